@@ -40,7 +40,13 @@ separately.  `--dist-backend gloo` stages every transfer through host memory:
 the one-GPU rehearsal of the N>1 path (all ranks on one device with
 RT0_BENCH_DEVICE=0, tests/test_bench_dist.py).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the
+headline figure needs: set-up, W warm-up steps, K timed steps, the outputs
+(`--dump-outputs DIR`: the HDR image of the last timed step as DIR/image.npy,
+float32; an image over 48 MB as a fixed, seeded sample of its pixels) and ONE
+JSON line on rank 0 with `value` and `ms_per_step`.  Everything else runs
+only with `--full`: at N > 1 the other scaling mode's job, the GPU clock
+sampled during the timed region, the secondary line (c2, c4), and
 `roofline` (VALU FP32: algorithmic FLOP/sample from SURVEY 8d x counted events,
 over the kernel's HIP-event time; HBM traffic from the committed PMC passes)
 and, at N=1, `cpu_baseline` (the JS CPU integrator
@@ -531,16 +537,80 @@ def valu_rates():
     return None
 
 
+DUMP_MAX_BYTES = 48 << 20  # of the 64 MB a dump may take
+
+
+def dump_outputs(path, image):
+    """--dump-outputs: the last timed step's HDR image (a device tensor,
+    H x W x 4 float32) as path/image.npy.  An image over DUMP_MAX_BYTES is
+    written as the same pixels every run: a sorted sample drawn without
+    replacement by a generator seeded with 0, N x 4."""
+    import numpy as np
+    a = np.ascontiguousarray(image.cpu().numpy(), dtype=np.float32)
+    if a.nbytes > DUMP_MAX_BYTES:
+        px = a.reshape(-1, a.shape[-1])
+        n = DUMP_MAX_BYTES // (4 * a.shape[-1])
+        a = px[np.sort(np.random.default_rng(0).choice(px.shape[0], size=n, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "image.npy"), a)
+
+
+def result_line(args, wl, world, weak, value, ms_per_step, job):
+    """The result line of a plain run (--full adds its entries to it)."""
+    import numpy as np
+    from rt0 import workloads
+    W, H = wl["width"], wl["height"]
+    mdb = wl["constants"].get("MAX_DIFF_BOUNCES", 4)
+    out = {
+        "metric": "Msamples/sec (pixels x spp / s) at 1024^2 Cornell, 8 bounces" if args.config == "c2"
+        else "Msamples/sec (pixels x spp / s), BASELINE workload %s" % args.config,
+        "value": round(value, 3),
+        "unit": "Msamples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True,
+        "scaling": "weak" if weak else "strong",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (the reference's own scene grammar and materials; no external data)",
+        "config": {"workload": "%s (%s): %s" % (args.config, wl["fixture"], wl["doc"]),
+                   "width": W, "height": H, "spp": wl["spp"], "max_diff_bounces": mdb,
+                   "parallelism": ("row-band x%d (16-row bands)" % world) if not workloads.restir(wl)
+                   else ("round-robin row bands x%d + reservoir halo exchange" % world),
+                   "dist_backend": args.dist_backend if world > 1 else None,
+                   "kernel": "scene-specialised (hipRTC JIT)" if args.jit else "ahead-of-time",
+                   "executor_compat": bool(args.executor_compat)},
+    }
+    if wl.get("baseline_spp") and wl["baseline_spp"] != wl["spp"]:
+        out["config"]["spp_note"] = ("BASELINE.md quotes this config at %d spp; one bench step renders %d passes "
+                                     "(Msamples/s is per sample either way)" % (wl["baseline_spp"], wl["spp"]))
+    out["config"]["job"] = ("%dx%d x %d spp per step over %d GPU(s) (%s scaling: %s)"
+                            % (W, H, wl["spp"], world, "weak" if weak else "strong",
+                               "per-GPU work of the N = 1 step" if weak else "the N = 1 step's job split N ways"))
+    if job.gather_ms:
+        out["gather_ms_per_step"] = round(float(np.mean(job.gather_ms)), 3)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="c2", help="workload of rt0/workloads.json: c1 c2 c2_refcaps c3 c4 c5")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: the event "
+                         "census and roofline, the GPU clock during the timed region, the secondary line (c2, c4), "
+                         "the CPU baselines and, at N > 1, the other scaling mode's job")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0: write the last timed step's HDR image (H x W x 4 float32, what a caller of the "
+                         "timed path reads back) as DIR/image.npy; over 48 MB, a fixed seeded sample of its pixels")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--secondary", action="store_true", help="(default now; kept for old command lines)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary line: c2 at MAX_DIFF_BOUNCES=4, c4 at MAX_DIFF_BOUNCES=12")
+                    help="with --full: skip the secondary line: c2 at MAX_DIFF_BOUNCES=4, c4 at MAX_DIFF_BOUNCES=12")
     ap.add_argument("--jit", type=int, default=1, help="1: scene-specialised kernels (default), 0: ahead-of-time")
     ap.add_argument("--executor-compat", action="store_true",
                     help="rt0_set_executor_compat(1): the reference executor's reservoir stores (ReSTIR workloads)")
@@ -557,6 +627,8 @@ def main():
                          "reads the previous pass's reservoirs).")
     ap.add_argument("--spp", type=int, default=None, help="passes per step at N = 1 (default: the workload's)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(relaunch(args.gpus))
@@ -622,12 +694,12 @@ def main():
         return span
 
     job = make_job(wl)
-    clock = ClockSampler(torch, local)
+    clock = ClockSampler(torch, local) if args.full else None
     dt = timed(job, clock)
-    # N > 1, progressive: the other scaling mode's job after the primary one,
-    # every rank, so a SCALE record holds both the fixed job and the per-GPU one
+    # --full, N > 1, progressive: the other scaling mode's job after the primary
+    # one, every rank, so a SCALE record holds both the fixed job and the per-GPU one
     second = None
-    if world > 1 and not workloads.restir(wl):
+    if args.full and world > 1 and not workloads.restir(wl):
         mode2 = "strong" if weak else "weak"
         wl2 = dict(wl, spp=base_spp * world if mode2 == "weak" else base_spp)
         job2 = make_job(wl2)
@@ -645,6 +717,14 @@ def main():
         if second:
             root, ext = os.path.splitext(args.save_image)
             np.save(root + "_secondary" + (ext or ".npy"), second[2].final_image().cpu().numpy()[:H])
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, job.final_image()[:H])
+    if not args.full:
+        print(json.dumps(result_line(args, wl, world, weak, value, ms_per_step, job)), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
 
     first_timed = 1 + args.warmup * wl["spp"]
     cnt = count_events(rt0, wl, local, first_timed, args.executor_compat)
@@ -706,36 +786,8 @@ def main():
                        + v["SQ_INSTS_VALU_TRANS_F32"] * rates[1]) / 1024.0
             roof["valu_busy"] = round(busy_ns / (kern_launch_s * 1e9), 4)
             roof["valu_rates_source"] = rates[2]
-    mdb = wl["constants"].get("MAX_DIFF_BOUNCES", 4)
-    out = {
-        "metric": "Msamples/sec (pixels x spp / s) at 1024^2 Cornell, 8 bounces" if args.config == "c2"
-        else "Msamples/sec (pixels x spp / s), BASELINE workload %s" % args.config,
-        "value": round(value, 3),
-        "unit": "Msamples/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True,
-        "scaling": "weak" if weak else "strong",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic (the reference's own scene grammar and materials; no external data)",
-        "config": {"workload": "%s (%s): %s" % (args.config, wl["fixture"], wl["doc"]),
-                   "width": W, "height": H, "spp": wl["spp"], "max_diff_bounces": mdb,
-                   "parallelism": ("row-band x%d (16-row bands)" % world) if not workloads.restir(wl)
-                   else ("round-robin row bands x%d + reservoir halo exchange" % world),
-                   "dist_backend": args.dist_backend if world > 1 else None,
-                   "kernel": "scene-specialised (hipRTC JIT)" if args.jit else "ahead-of-time",
-                   "executor_compat": bool(args.executor_compat)},
-        "roofline": roof,
-    }
-    if wl.get("baseline_spp") and wl["baseline_spp"] != wl["spp"]:
-        out["config"]["spp_note"] = ("BASELINE.md quotes this config at %d spp; one bench step renders %d passes "
-                                     "(Msamples/s is per sample either way)" % (wl["baseline_spp"], wl["spp"]))
-    out["config"]["job"] = ("%dx%d x %d spp per step over %d GPU(s) (%s scaling: %s)"
-                            % (W, H, wl["spp"], world, "weak" if weak else "strong",
-                               "per-GPU work of the N = 1 step" if weak else "the N = 1 step's job split N ways"))
+    out = result_line(args, wl, world, weak, value, ms_per_step, job)
+    out["roofline"] = roof
     if second:
         mode2, wl2, _, v2 = second
         out["secondary_%s_Msamples_s" % mode2] = round(v2, 3)
@@ -743,8 +795,6 @@ def main():
                                           "primary job with the same steps / warmup"
                                           % (W, H, wl2["spp"], world, mode2))
     out["gpu_clock"] = clock.report()
-    if job.gather_ms:
-        out["gather_ms_per_step"] = round(float(np.mean(job.gather_ms)), 3)
     if not args.no_secondary and world == 1 and args.config in ("c2", "c4"):
         # after the timed region, same renderer: C2 at the reference's caps
         # (MAX_DIFF_BOUNCES = 4, SURVEY 8d "report both"); C4 at its true depth

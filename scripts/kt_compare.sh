@@ -9,7 +9,7 @@ mkdir -p "$O"
 for v in "$@"; do
   name=${v%%:*}; envs=${v#*:}
   env $envs timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$O/kt_$name" -o run -- \
-    python bench.py --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-secondary > "$O/kt_$name.log" 2>&1
+    python bench.py --full --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-secondary > "$O/kt_$name.log" 2>&1
   rc=$?; echo "kt $name rc=$rc"; [ $rc -ne 0 ] && { tail -5 "$O/kt_$name.log"; exit $rc; }
   python3 scripts/kt_summary.py "$O/kt_$name.json" "$O/kt_$name" 1
   python3 - "$O/kt_$name" <<'PY'

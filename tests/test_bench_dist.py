@@ -43,9 +43,20 @@ def run_bench(tmp_path, config, gpus, extra=(), tag=""):
 @pytest.mark.gpu
 @pytest.mark.parametrize("config", ["c2", "c3", "c5"])
 def test_bench_two_ranks_match_one(tmp_path, gpu_required, config):
-    one, a = run_bench(tmp_path, config, 1)
+    one, a = run_bench(tmp_path, config, 1, ["--dump-outputs", str(tmp_path / "dump")])
     two, b = run_bench(tmp_path, config, 2, ["--dist-backend", "gloo"])
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2
+    # a plain run: the headline line only, and the dumped output is the image
+    # (C5's 4096^2 image: a sample of its pixels within the size limit)
+    assert one["ms_per_step"] > 0 and "roofline" not in one and "cpu_baseline" not in one
+    d = np.load(tmp_path / "dump" / "image.npy")
+    assert d.dtype == np.float32 and d.nbytes <= 64 << 20
+    if a.nbytes <= 48 << 20:
+        assert np.array_equal(d, a)
+    else:
+        px = a.reshape(-1, 4)
+        idx = np.sort(np.random.default_rng(0).choice(len(px), size=(48 << 20) // 16, replace=False))
+        assert np.array_equal(d, px[idx])
     assert two["config"]["dist_backend"] == "gloo"
     assert a.shape == b.shape
     assert np.isfinite(a).all() and a[..., :3].mean() > 0.0
@@ -56,7 +67,7 @@ def test_bench_two_ranks_match_one(tmp_path, gpu_required, config):
 @pytest.mark.gpu
 @pytest.mark.parametrize("config", ["c2", "c4"])
 def test_bench_both_scalings_two_ranks(tmp_path, gpu_required, config):
-    """At N>1 a progressive workload's line carries both jobs: its default
+    """At N>1 a progressive workload's `--full` line carries both jobs: its default
     (C2 strong: BASELINE's fixed 1024^2 job split N ways; C4 weak: N x spp
     passes, each rank its rows of all of them) as `value`, and the other one
     as secondary_<mode>_Msamples_s.  Both gathered images equal one rank's
@@ -64,7 +75,7 @@ def test_bench_both_scalings_two_ranks(tmp_path, gpu_required, config):
     spp = 4
     one, a = run_bench(tmp_path, config, 1, ["--spp", str(spp)])
     one2, a2 = run_bench(tmp_path, config, 1, ["--spp", str(2 * spp)], tag="x2")
-    two, b = run_bench(tmp_path, config, 2, ["--dist-backend", "gloo", "--spp", str(spp)])
+    two, b = run_bench(tmp_path, config, 2, ["--full", "--dist-backend", "gloo", "--spp", str(spp)])
     default = {"c2": "strong", "c4": "weak"}[config]
     other = "weak" if default == "strong" else "strong"
     assert two["scaling"] == default, two["scaling"]

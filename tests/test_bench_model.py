@@ -150,3 +150,21 @@ def test_kt_summary_split_restir_pass_is_its_span(tmp_path):
     assert res["kept"] == 2 and res["median_ms"] == pytest.approx(6.9, abs=1e-6)
     assert res["per_kernel_median_ms"]["rt0_jit_pass"] == pytest.approx(9.0, abs=1e-6)
     assert res["per_kernel_median_ms"]["dispatches_per_pass"]["rt0_jit_resolve"] == 3
+
+
+def test_dump_outputs_writes_the_image_or_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a small image is written whole as float32; one over the
+    size limit as the same sorted, seeded sample of its pixels every time."""
+    import numpy as np
+    import torch
+    img = torch.arange(8 * 6 * 4, dtype=torch.float32).reshape(8, 6, 4)
+    bench.dump_outputs(str(tmp_path / "a"), img)
+    a = np.load(tmp_path / "a" / "image.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, img.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 10 * 16)  # room for 10 of the 48 pixels
+    bench.dump_outputs(str(tmp_path / "b"), img)
+    bench.dump_outputs(str(tmp_path / "c"), img)
+    b, c = np.load(tmp_path / "b" / "image.npy"), np.load(tmp_path / "c" / "image.npy")
+    assert b.shape == (10, 4) and b.dtype == np.float32 and np.array_equal(b, c)
+    rows = (b[:, 0] / 4).astype(int)  # pixel k holds 4k .. 4k + 3
+    assert (np.diff(rows) > 0).all() and np.array_equal(b, img.numpy().reshape(-1, 4)[rows])
