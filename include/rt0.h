@@ -134,6 +134,24 @@ int rt0_get_scene(const rt0_ctx *ctx, rt0_mesh *meshes, int max_meshes, int *n_m
 int rt0_set_model(rt0_ctx *ctx, int model, const float *positions, int n_vertices, const int32_t *indices,
                   int n_triangles);
 int rt0_model_info(rt0_ctx *ctx, int *n_triangles, int *bvh_depth);
+/* Test hooks of the triangle path (not used by any renderer).
+ * Ray queries: n rays (origins / dirs = n x 3 floats, tmax = n bounds or NULL
+ * for none) through the device code of the walk, one lane per ray; builds
+ * the BVH first if needed, like rt0_model_info.  mode 0: the closest-hit walk
+ * (bvh_closest), 1: the occlusion walk (the first hit before tmax), 2: a
+ * plain loop over every triangle in leaf order with the same triangle test
+ * and no boxes.  t_out[i] = the hit's t (tmax[i], or the integrator's "no
+ * hit" distance 1e4 without tmax, on a miss), tri_out[i] = the leaf-order
+ * triangle index or -1.  1/d is taken as the integrator's call sites take it. */
+int rt0_trace_rays(rt0_ctx *ctx, int n, const float *origins, const float *dirs, const float *tmax, int mode,
+                   float *t_out, int32_t *tri_out);
+/* The device tree as the walks read it: nodes_out = max(1, n_triangles - 1)
+ * x 16 words (BvhNode: floats lx0 ly0 lz0 rx0, lx1 ly1 lz1 ry0, rz0 rx1 ry1
+ * rz1, then int32 left, right (>= 0 node, < 0 leaf ~triangle), 2 x pad),
+ * tris_out = n_triangles x 12 words (TriDev: v0 xyz, int32 model, e0 xyz,
+ * int32 cull, e1 xyz, float eps) in leaf order; *treelet = the leading nodes
+ * numbered breadth-first.  Sizes come from rt0_model_info; any may be NULL. */
+int rt0_debug_read_bvh(rt0_ctx *ctx, void *nodes_out, void *tris_out, int *treelet);
 /* Wavefront OBJ (v / f records; polygons fan-triangulated; v/vt/vn and
  * negative indices accepted) -> malloc'd positions / indices (rt0_free). */
 int rt0_obj_read(const char *path, float **positions, int *n_vertices, int32_t **indices, int *n_triangles);

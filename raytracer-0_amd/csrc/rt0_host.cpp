@@ -28,6 +28,9 @@ extern "C" hipError_t rt0_launch_pass(int variant, const LaunchParams *p, dim3 g
 extern "C" hipError_t rt0_launch_tonemap(const float4 *acc, uchar4 *out, int n, float cont, int mode,
                                          hipStream_t stream);
 extern "C" hipError_t rt0_launch_sum(const LaunchParams *p, dim3 grid, hipStream_t stream);
+extern "C" hipError_t rt0_launch_trace(const LaunchParams *p, int n, const float *org, const float *dir,
+                                       const float *tmax, int mode, float *t_out, int32_t *tri_out,
+                                       hipStream_t stream);
 extern "C" hipError_t rt0_bvh_build(int n, const float *d_v, const int32_t *d_model, float3 lo, float3 hi,
                                     BvhNode *d_nodes, TriDev *d_tris, int *depth_out,
                                     hipStream_t s);
@@ -583,6 +586,69 @@ int rt0_model_info(rt0_ctx *c, int *n_triangles, int *bvh_depth) {
   }
   if (n_triangles) *n_triangles = c->n_tris;
   if (bvh_depth) *bvh_depth = c->bvh_depth;
+  return RT0_OK;
+}
+
+// Test hook: rays through the walk's device code (rt0_kernels.hip
+// rt0_trace_kernel).  One device block holds the inputs and the outputs.
+int rt0_trace_rays(rt0_ctx *c, int n, const float *origins, const float *dirs, const float *tmax, int mode,
+                   float *t_out, int32_t *tri_out) {
+  if (!c || n < 0 || mode < 0 || mode > 2) return RT0_E_ARG;
+  if (n > 0 && (!origins || !dirs || !t_out || !tri_out)) return RT0_E_ARG;
+  if (!c->has_scene) return fail(c, RT0_E_STATE, "rt0_trace_rays before rt0_set_scene*");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->bvh_dirty) {
+    int rc = build_bvh(c);
+    if (rc != RT0_OK) return rc;
+  }
+  if (n == 0) return RT0_OK;
+  const size_t N = (size_t)n;
+  float *d = nullptr;  // origins 3n | dirs 3n | tmax n | t n | tri n
+  HIPCHK(c, hipMalloc(&d, 9 * N * sizeof(float)));
+  float *d_o = d, *d_d = d + 3 * N, *d_tm = d + 6 * N, *d_t = d + 7 * N;
+  int32_t *d_i = reinterpret_cast<int32_t *>(d + 8 * N);
+  LaunchParams p;
+  memset(&p, 0, sizeof p);
+  p.bvh = c->d_bvh;
+  p.tris = c->d_tris;
+  p.n_tris = c->n_tris;
+  p.treelet = c->treelet;
+  hipError_t e = hipMemcpyAsync(d_o, origins, 3 * N * sizeof(float), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_d, dirs, 3 * N * sizeof(float), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess && tmax) e = hipMemcpyAsync(d_tm, tmax, N * sizeof(float), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    if (c->n_tris > 0) {
+      e = rt0_launch_trace(&p, n, d_o, d_d, tmax ? d_tm : nullptr, mode, d_t, d_i, c->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(t_out, d_t, N * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(tri_out, d_i, N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+    } else {  // no triangles: every ray misses
+      for (int i = 0; i < n; i++) {
+        t_out[i] = tmax ? tmax[i] : 1e4f;
+        tri_out[i] = -1;
+      }
+    }
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(d);
+  if (e != hipSuccess) return fail(c, RT0_E_HIP, std::string("rt0_trace_rays: ") + hipGetErrorString(e));
+  return RT0_OK;
+}
+
+int rt0_debug_read_bvh(rt0_ctx *c, void *nodes_out, void *tris_out, int *treelet) {
+  if (!c) return RT0_E_ARG;
+  if (!c->has_scene) return fail(c, RT0_E_STATE, "rt0_debug_read_bvh before rt0_set_scene*");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->bvh_dirty) {
+    int rc = build_bvh(c);
+    if (rc != RT0_OK) return rc;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (treelet) *treelet = c->treelet;
+  if (c->n_tris == 0) return RT0_OK;
+  if (nodes_out)
+    HIPCHK(c, hipMemcpy(nodes_out, c->d_bvh, (size_t)std::max(1, c->n_tris - 1) * sizeof(BvhNode),
+                        hipMemcpyDeviceToHost));
+  if (tris_out) HIPCHK(c, hipMemcpy(tris_out, c->d_tris, (size_t)c->n_tris * sizeof(TriDev), hipMemcpyDeviceToHost));
   return RT0_OK;
 }
 

@@ -390,14 +390,36 @@ DEV bool tri_test(const TriDev &T, v3 o, v3 d, float tmin, float &t) {
   return t > EPSILON && t < tmin;
 }
 // slab test of a child box: entry distance, or +inf when the ray misses it or
-// enters beyond tmin
+// enters beyond tmin.  Conservative: a box is never rejected
+// because of the test's own rounding, so the walk finds what a loop over every
+// triangle finds.  With u = 2^-24:
+//  * a slab distance (x - o) * inv carries one rounding of the difference,
+//    one of the product and the rcp's 1 ulp (2u): a relative error <= 4u.  If
+//    the exact ray meets the closed box at t, the computed entry is <=
+//    t (1 + 4u) and the computed exit >= t (1 - 4u), so entry <= exit *
+//    (1 + 4u) / (1 - 4u): the exit is widened by 1 + 10u (8u, the rounding of
+//    that product, a spare u).  Without it a zero-thickness box (an
+//    axis-aligned triangle's) or any box whose edge or corner the ray passes
+//    was rejected whenever its two equal distances rounded apart.
+//  * the entry is compared with tmin, a tri_test t with its own rounding
+//    (about 20 operations, each error weighted by the triangle's
+//    conditioning, not bounded in general): the entry is shrunk by 32u =
+//    4u + 28u for a tri_test within 14 ulp of the exact distance, so that of
+//    coplanar overlapping triangles the least t wins as it does in a loop.
+//  * a direction component of exactly 0 makes inv infinite, and an origin
+//    exactly in the plane of a box face makes the difference 0: 0 * inf = NaN
+//    dropped that face and left its slab's other infinity as both entry and
+//    exit -- a miss, although the ray runs inside the closed slab.  A zero
+//    difference counts as just inside (-+1e-30: below every non-zero
+//    difference of two floats of usable size, so nothing else changes).
 DEV float box_enter(float x0, float y0, float z0, float x1, float y1, float z1, v3 o, v3 inv, float tmin) {
-  const float tx0 = (x0 - o.x) * inv.x, tx1 = (x1 - o.x) * inv.x;
-  const float ty0 = (y0 - o.y) * inv.y, ty1 = (y1 - o.y) * inv.y;
-  const float tz0 = (z0 - o.z) * inv.z, tz1 = (z1 - o.z) * inv.z;
+  constexpr float IN = 1e-30f, WIDE = 1.0f + 10.0f * 0x1p-24f, NEAR = 1.0f - 32.0f * 0x1p-24f;
+  const float tx0 = ((x0 - o.x) - IN) * inv.x, tx1 = ((x1 - o.x) + IN) * inv.x;
+  const float ty0 = ((y0 - o.y) - IN) * inv.y, ty1 = ((y1 - o.y) + IN) * inv.y;
+  const float tz0 = ((z0 - o.z) - IN) * inv.z, tz1 = ((z1 - o.z) + IN) * inv.z;
   const float tn = fmaxf(fmaxf(fminf(tx0, tx1), fminf(ty0, ty1)), fmaxf(fminf(tz0, tz1), 0.0f));
   const float tf = fminf(fminf(fmaxf(tx0, tx1), fmaxf(ty0, ty1)), fmaxf(tz0, tz1));
-  return (tn <= tf && tn < tmin) ? tn : F_INF;
+  return (tn <= tf * WIDE && tn * NEAR < tmin) ? tn : F_INF;
 }
 // The BVH's top levels in LDS (RT0_TREELET nodes of capacity; the
 // scene-specialised modules of scenes with triangle models): the host numbers

@@ -40,6 +40,38 @@ __global__ __launch_bounds__(256) void rt0_tonemap_kernel(const float4 *__restri
   out[i] = make_uchar4(g(a.x), g(a.y), g(a.z), 255);
 }
 
+// Ray queries of the triangle path (rt0_trace_rays, a test hook): one lane
+// per ray in blocks of 256 (BvhStack's stride).  mode 0 = bvh_closest, 1 =
+// bvh_closest<true> (occlusion), 2 = every triangle in leaf order through the
+// same tri_test with no boxes: what the walk has to reproduce.  1/d as the
+// integrator's call sites take it (frcp per component).
+__global__ __launch_bounds__(256) void rt0_trace_kernel(const LaunchParams P, int n, const float *__restrict__ org,
+                                                        const float *__restrict__ dir,
+                                                        const float *__restrict__ tmax, int mode,
+                                                        float *__restrict__ t_out, int32_t *__restrict__ tri_out) {
+  treelet_load(P);
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const v3 o = mk(org[3 * i], org[3 * i + 1], org[3 * i + 2]);
+  const v3 d = mk(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]);
+  float tmin = tmax ? tmax[i] : INF_T;
+  int best = -1;
+  if (mode == 2) {
+    for (int k = 0; k < P.n_tris; k++) {
+      float t;
+      if (tri_test(P.tris[k], o, d, tmin, t)) {
+        tmin = t;
+        best = k;
+      }
+    }
+  } else {
+    const v3 m = mk(frcp(d.x), frcp(d.y), frcp(d.z));
+    best = mode == 1 ? bvh_closest<true>(P, o, d, m, tmin) : bvh_closest<false>(P, o, d, m, tmin);
+  }
+  t_out[i] = tmin;
+  tri_out[i] = best;
+}
+
 // ------------------------------------------------------------ launchers
 extern "C" hipError_t rt0_launch_pass_v0(const LaunchParams *, dim3, hipStream_t);
 extern "C" hipError_t rt0_launch_pass_v1(const LaunchParams *, dim3, hipStream_t);
@@ -60,6 +92,14 @@ extern "C" hipError_t rt0_launch_pass(int variant, const LaunchParams *p, dim3 g
 
 extern "C" hipError_t rt0_launch_sum(const LaunchParams *p, dim3 grid, hipStream_t stream) {
   hipLaunchKernelGGL(rt0_sum_kernel, dim3(grid.x, grid.y), dim3(256), 0, stream, *p);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t rt0_launch_trace(const LaunchParams *p, int n, const float *org, const float *dir,
+                                       const float *tmax, int mode, float *t_out, int32_t *tri_out,
+                                       hipStream_t stream) {
+  hipLaunchKernelGGL(rt0_trace_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, *p, n, org, dir, tmax, mode, t_out,
+                     tri_out);
   return hipGetLastError();
 }
 

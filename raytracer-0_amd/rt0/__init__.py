@@ -32,7 +32,7 @@ EXPORTS = ["rt0_create", "rt0_destroy", "rt0_last_error", "rt0_parse_config", "r
            "rt0_set_halo", "rt0_read_halo_misses", "rt0_set_jit", "rt0_set_executor_compat", "rt0_set_texture_filter", "rt0_set_defer_light_sampling", "rt0_set_wavefront", "rt0_jit_compile", "rt0_set_counting",
            "rt0_read_counters", "rt0_read_counters_n", "rt0_last_kernel_ms", "rt0_last_render_path", "rt0_version", "rt0_tonemap_ex", "rt0_png_decode", "rt0_png_read",
            "rt0_png_write", "rt0_pfm_write", "rt0_free", "rt0_set_texture", "rt0_set_cubemap", "rt0_jpeg_decode", "rt0_jpeg_read", "rt0_set_model", "rt0_model_info", "rt0_obj_read",
-           "rt0_set_temporal_frames", "rt0_set_viewport", "rt0_scratch_bytes"]
+           "rt0_set_temporal_frames", "rt0_set_viewport", "rt0_scratch_bytes", "rt0_trace_rays", "rt0_debug_read_bvh"]
 
 TEX_NOISE = 4  # RT0_TEX_NOISE: the u_rnd_tex unit of rt0_set_texture
 TONEMAP_GAMMA, TONEMAP_ACES, TONEMAP_REINHARD = 0, 1, 2
@@ -101,6 +101,8 @@ def lib():
                                   P(c_int)]),
         "rt0_set_model": (c_int, [c_void_p, c_int, fp, c_int, P(ctypes.c_int32), c_int]),
         "rt0_model_info": (c_int, [c_void_p, P(c_int), P(c_int)]),
+        "rt0_trace_rays": (c_int, [c_void_p, c_int, fp, fp, fp, c_int, fp, P(ctypes.c_int32)]),
+        "rt0_debug_read_bvh": (c_int, [c_void_p, c_void_p, c_void_p, P(c_int)]),
         "rt0_obj_read": (c_int, [ctypes.c_char_p, P(fp), P(c_int), P(P(ctypes.c_int32)), P(c_int)]),
         "rt0_set_camera": (c_int, [c_void_p, fp, fp, fp]),
         "rt0_set_texture": (c_int, [c_void_p, c_int, c_int, c_int, P(ctypes.c_uint8)]),
@@ -390,6 +392,53 @@ class Renderer:
         n, d = ctypes.c_int(), ctypes.c_int()
         self._chk(lib().rt0_model_info(self.h, ctypes.byref(n), ctypes.byref(d)))
         return n.value, d.value
+
+    def set_scene(self, meshes, n_meshes, n_sdfs, n_models, lights):
+        """Test hook: rt0_set_scene from flattened records, e.g. get_scene()'s
+        Mesh list with a field changed (mat_opts |= 8 on a TRIANGLE entry =
+        back-face culling)."""
+        arr = (Mesh * max(1, len(meshes)))(*meshes)
+        li = (ctypes.c_int32 * max(1, len(lights)))(*lights)
+        self._chk(lib().rt0_set_scene(self.h, arr, n_meshes, n_sdfs, n_models, li, len(lights)))
+
+    def trace_rays(self, origins, dirs, tmax=None, mode=0):
+        """Test hook: rays through the triangle walk's device code
+        (rt0_trace_rays).  origins / dirs float32 [n, 3], tmax float32 [n] or
+        None; mode 0 closest-hit walk, 1 occlusion walk, 2 loop over every
+        triangle.  Returns (t float32 [n], leaf-order triangle int32 [n], -1 =
+        miss)."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError("origins and dirs differ in length")
+        tm = None
+        if tmax is not None:
+            tm = np.ascontiguousarray(tmax, np.float32).reshape(-1)
+            if tm.shape[0] != n:
+                raise ValueError("tmax and origins differ in length")
+        t = np.empty(n, np.float32)
+        tri = np.empty(n, np.int32)
+        self._chk(lib().rt0_trace_rays(self.h, n, _fp(o), _fp(d), _fp(tm), int(mode), _fp(t),
+                                       tri.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        return t, tri
+
+    BVH_NODE = np.dtype([("lo_l", "<f4", 3), ("rx0", "<f4"), ("hi_l", "<f4", 3), ("ry0", "<f4"), ("rz0", "<f4"),
+                         ("hi_r", "<f4", 3), ("left", "<i4"), ("right", "<i4"), ("pad", "<i4", 2)])
+    TRI_DEV = np.dtype([("v0", "<f4", 3), ("model", "<i4"), ("e0", "<f4", 3), ("cull", "<i4"), ("e1", "<f4", 3),
+                        ("eps", "<f4")])
+
+    def read_bvh(self):
+        """Test hook: the device tree (rt0_debug_read_bvh) as structured arrays
+        (nodes BVH_NODE [max(1, n - 1)], triangles TRI_DEV [n] in leaf order)
+        and the number of leading breadth-first (treelet) nodes."""
+        n, _ = self.model_info()
+        nodes = np.zeros(max(1, n - 1) if n else 0, self.BVH_NODE)
+        tris = np.zeros(n, self.TRI_DEV)
+        tl = ctypes.c_int()
+        self._chk(lib().rt0_debug_read_bvh(self.h, nodes.ctypes.data_as(ctypes.c_void_p) if n else None,
+                                           tris.ctypes.data_as(ctypes.c_void_p) if n else None, ctypes.byref(tl)))
+        return nodes, tris, tl.value
 
     def set_texture(self, unit, rgba8):
         """loadTexture (index.js:699-728): unit 0..3 = u_tex0..3, TEX_NOISE = u_rnd_tex.

@@ -265,3 +265,17 @@ def test_wavefront_restir_models_viewport_and_shards(cfgs, gpu_required):
     assert not s1[0][:32, :, :3].any() and s1[0][32:, :, :3].any()
     close_and_mostly_identical(m0, m1, "reservoir main")
     close_and_mostly_identical(s0[..., :3], s1[..., :3], "samples")
+
+
+def test_wavefront_restir_slot_chunks_exact(cfgs, gpu_required, monkeypatch):
+    """The ReSTIR rounds of a models scene under a budget (RT0_WF_BYTES)
+    below one frame's path slots -- a slot takes more than 100 bytes, so
+    64 * 64 * 100 bytes hold only part of a 64 x 64 frame -- run as slot
+    chunks of whole regions: the same bits as the unchunked render, samples
+    and reservoirs, over a 3-pass chain."""
+    s0, m0, a0, p0 = restir_chain(cfgs, True, n=3)
+    monkeypatch.setenv("RT0_WF_BYTES", str(64 * 64 * 100))
+    s1, m1, a1, p1 = restir_chain(cfgs, True, n=3)
+    assert p0 == "wavefront" and p1 == "wavefront", (p0, p1)
+    assert np.array_equal(s0, s1) and np.array_equal(m0, m1) and np.array_equal(a0, a1)
+    assert s1[..., :3].mean() > 0.0
