@@ -138,7 +138,8 @@ int rt0_model_info(rt0_ctx *ctx, int *n_triangles, int *bvh_depth);
  * Ray queries: n rays (origins / dirs = n x 3 floats, tmax = n bounds or NULL
  * for none) through the device code of the walk, one lane per ray; builds
  * the BVH first if needed, like rt0_model_info.  mode 0: the closest-hit walk
- * (bvh_closest), 1: the occlusion walk (the first hit before tmax), 2: a
+ * (bvh_closest, on the node-visit step BvhWalk that every walk kernel
+ * shares), 1: the occlusion walk (the first hit before tmax), 2: a
  * plain loop over every triangle in leaf order with the same triangle test
  * and no boxes.  t_out[i] = the hit's t (tmax[i], or the integrator's "no
  * hit" distance 1e4 without tmax, on a miss), tri_out[i] = the leaf-order

@@ -113,9 +113,6 @@ DEV float flog(float x) { return __logf(x); }
 #ifndef RT0_WALK_ROOT_TEST  // light-sampling kernel drops walk jobs that miss the root's child boxes
 #define RT0_WALK_ROOT_TEST 1
 #endif
-#ifndef RT0_WALK_SPEC  // rt0_jit_walk postpones leaf tests until half the busy lanes hold one
-#define RT0_WALK_SPEC 1
-#endif
 // ReSTIR reservoir textures (index.js:149-163) as interleaved pairs: texel i
 // of a main plane at float4 2i of its pair buffer, the aux plane's at 2i + 1
 // (rt0_host.cpp alloc_buffers), so a bilinear tap's main and aux texels share
@@ -506,6 +503,69 @@ struct BvhStack {
   DEV int get(int sp) const { return s[256 * sp]; }
 #endif
 };
+// One node visit of a depth-first walk, the step every walk of the tree shares
+// (bvh_closest, walk_body, wf_walk_body): the entry distances of the node's
+// two child boxes (F_INF: not entered before the bound, or a leaf), the
+// children's links, and the leaf children that were entered, as triangle
+// indices left before right (-1: none).
+struct BvhVisit {
+  float tl, tr;
+  int cl, cr, l0, l1;
+};
+// A lane's place in such a walk.  Per node: visit(), the walk's own leaf
+// tests on v.l0 / v.l1 (which may lower its bound), then next(v) -- whose
+// choice uses the distances found before those tests.
+struct BvhWalk {
+  BvhStack stk;
+  int node, sp, guard;  // node < 0: the traversal is over
+  // (stale stack entries of an earlier ray are never read: sp restarts at 0)
+  DEV void start(const LaunchParams &P) {
+    node = 0;
+    sp = 0;
+    guard = 0;
+  }
+  DEV BvhVisit visit(const LaunchParams &P, v3 o, v3 inv, float tmax) const {
+    float4 a, b, c;
+    int4 lk;
+    bvh_fetch(P, reinterpret_cast<const float4 *>(P.bvh), node, a, b, c, lk);
+    BvhVisit v;
+    v.tl = box_enter(a.x, a.y, a.z, b.x, b.y, b.z, o, inv, tmax);
+    v.tr = box_enter(a.w, b.w, c.x, c.y, c.z, c.w, o, inv, tmax);
+    v.cl = lk.x;
+    v.cr = lk.y;
+    v.l0 = v.l1 = -1;
+    if (v.tl != F_INF && v.cl < 0) {
+      v.l0 = ~v.cl;
+      v.tl = F_INF;
+    }
+    if (v.tr != F_INF && v.cr < 0) {
+      if (v.l0 < 0) v.l0 = ~v.cr;
+      else v.l1 = ~v.cr;
+      v.tr = F_INF;
+    }
+    return v;
+  }
+  // the nearer entered inner child next, the far one on the stack; else the
+  // one entered; else the stack's top.  False once the traversal is over.
+  DEV bool next(const LaunchParams &P, const BvhVisit &v) {
+    if (v.tl != F_INF && v.tr != F_INF) {
+      const bool lfirst = v.tl <= v.tr;
+      stk.put(sp, lfirst ? v.cr : v.cl);
+      sp = min(sp + 1, RT0_BVH_STACK - 1);  // the build guarantees depth < RT0_BVH_STACK
+      node = lfirst ? v.cl : v.cr;
+    } else if (v.tl != F_INF) {
+      node = v.cl;
+    } else if (v.tr != F_INF) {
+      node = v.cr;
+    } else {
+      node = sp == 0 ? -1 : stk.get(--sp);
+    }
+    // a ray visits each of the n-1 nodes at most once: the cap only
+    // guarantees that every wave exits even on a corrupt tree
+    if (++guard > 2 * P.n_tris + 8) node = -1;
+    return node >= 0;
+  }
+};
 // the record counter of this wave's deferred light-sampling region
 DEV uint32_t *nee_wave_counter() {
   __shared__ uint32_t cnt[4];
@@ -540,61 +600,32 @@ DEV uint32_t wave_append(uint32_t *ctr) {
 template <bool ANY = false>
 DEV int bvh_closest(const LaunchParams &P, v3 o, v3 d, v3 inv, float &tmin, unsigned long long *cnt = nullptr,
                     int budget = 0x7fffffff, bool *complete = nullptr) {
-  BvhStack stk;
-  int sp = 0, node = 0, best = -1;
-  const float4 *__restrict__ nodes = reinterpret_cast<const float4 *>(P.bvh);
+  BvhWalk w;
+  w.start(P);
+  int best = -1;
   const TriDev *__restrict__ tris = P.tris;
-  // a ray visits each of the n-1 nodes at most once: the cap only guarantees
-  // that every wave exits even on a corrupt tree
-  for (int guard = 2 * P.n_tris + 8; guard > 0; --guard) {
+  BvhVisit v;
+  do {
     if (complete && budget-- <= 0) {
       *complete = false;
       break;
     }
-    float4 a, b, c;
-    int4 lk;
-    bvh_fetch(P, nodes, node, a, b, c, lk);
-    float tl = box_enter(a.x, a.y, a.z, b.x, b.y, b.z, o, inv, tmin);
-    float tr = box_enter(a.w, b.w, c.x, c.y, c.z, c.w, o, inv, tmin);
-    const int cl = lk.x, cr = lk.y;
+    v = w.visit(P, o, inv, tmin);
     if (cnt) ++cnt[0];  // counting instance: nodes visited (two child boxes each)
-    int l0 = -1, l1 = -1;
-    if (tl != F_INF && cl < 0) {
-      l0 = ~cl;
-      tl = F_INF;
-    }
-    if (tr != F_INF && cr < 0) {
-      if (l0 < 0) l0 = ~cr;
-      else l1 = ~cr;
-      tr = F_INF;
-    }
-    if (l0 >= 0) {
+    if (v.l0 >= 0) {
       float t;
-      if (cnt) cnt[1] += 1 + (l1 >= 0);  // triangle tests
-      if (tri_test(tris[l0], o, d, tmin, t)) {
+      if (cnt) cnt[1] += 1 + (v.l1 >= 0);  // triangle tests
+      if (tri_test(tris[v.l0], o, d, tmin, t)) {
         tmin = t;
-        best = l0;
+        best = v.l0;
       }
-      if (l1 >= 0 && tri_test(tris[l1], o, d, tmin, t)) {
+      if (v.l1 >= 0 && tri_test(tris[v.l1], o, d, tmin, t)) {
         tmin = t;
-        best = l1;
+        best = v.l1;
       }
       if (ANY && best >= 0) break;
     }
-    if (tl != F_INF && tr != F_INF) {
-      const bool lfirst = tl <= tr;
-      stk.put(sp, lfirst ? cr : cl);
-      sp = min(sp + 1, RT0_BVH_STACK - 1);  // the build guarantees depth < RT0_BVH_STACK
-      node = lfirst ? cl : cr;
-    } else if (tl != F_INF) {
-      node = cl;
-    } else if (tr != F_INF) {
-      node = cr;
-    } else {
-      if (sp == 0) break;
-      node = stk.get(--sp);
-    }
-  }
+  } while (w.next(P, v));
   return best;
 }
 
@@ -3288,15 +3319,14 @@ DEV void nee_body(const LaunchParams &P, Scene sc, Cfg cfg) {
 // lane whose ray is answered takes the wave's next job (an LDS counter), so
 // the wave walks on full lanes until its list runs dry instead of waiting for
 // its longest ray every 64 jobs.  One node (two child boxes) per iteration.
-// RT0_WALK_SPEC: walk_body with the leaf tests postponed (speculative
-// while-while traversal, Aila & Laine 2009): a lane whose node visit finds
-// leaf triangles keeps them pending and the wave tests pending leaves only
-// once half its busy lanes hold some (or every busy lane does), so the
-// triangle tests run on many lanes at once instead of splitting every
-// iteration into node lanes and leaf lanes.  An occlusion answer is a set
-// property (some triangle in (EPSILON, tmax)): the visiting order does not
-// change it.
-DEV void walk_body_spec(const LaunchParams &P) {
+// The leaf tests are postponed (speculative while-while traversal, Aila &
+// Laine 2009): a lane whose node visit finds leaf triangles keeps them
+// pending and the wave tests pending leaves only once half its busy lanes
+// hold some (or every busy lane does), so the triangle tests run on many
+// lanes at once instead of splitting every iteration into node lanes and leaf
+// lanes.  An occlusion answer is a set property (some triangle in (EPSILON,
+// tmax)): the visiting order does not change it.
+DEV void walk_body(const LaunchParams &P) {
   treelet_load(P);
   const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
   if (w >= (uint32_t)P.walk_waves) return;
@@ -3304,15 +3334,15 @@ DEV void walk_body_spec(const LaunchParams &P) {
   const WalkJob *__restrict__ jobs = P.walk_jobs + (size_t)w * (2u * RT0_NEE_REGIONS * (uint32_t)P.nee_cap);
   uint32_t *ctr = nee_wave_counter();
   *(volatile uint32_t *)ctr = 64u;  // every lane stores the same value: jobs 0..63 go by lane index
-  const float4 *__restrict__ nodes = reinterpret_cast<const float4 *>(P.bvh);
   const TriDev *__restrict__ tris = P.tris;
-  BvhStack stk;
+  BvhWalk wk;
+  wk.start(P);
   uint32_t j = threadIdx.x & 63u;
   bool have = false;
   v3 o = mk(0.f, 0.f, 0.f), d = o, inv = o;
   float tmax = 0.f;
   uint32_t slot2 = 0;
-  int node = 0, sp = 0, guard = 0, pa = -1, pb = -1;  // node -1: traversal over; pa/pb: pending leaves
+  int pa = -1, pb = -1;  // pending leaves
   auto load = [&]() {
     have = j < n;
     if (have) {
@@ -3322,156 +3352,35 @@ DEV void walk_body_spec(const LaunchParams &P) {
       inv = mk(frcp(d.x), frcp(d.y), frcp(d.z));
       tmax = jb.tmax;
       slot2 = jb.slot2;
-      node = 0;
-      sp = 0;
-      guard = 0;  // (stale stack entries are never read: sp restarts at 0)
+      wk.start(P);
       pa = pb = -1;
     }
   };
   load();
   while (__ballot(have) != 0ull) {
     // node phase: lanes without pending leaves visit their next node
-    if (have && pa < 0 && node >= 0) {
-      float4 a, b, c;
-      int4 lk;
-      bvh_fetch(P, nodes, node, a, b, c, lk);
-      float tl = box_enter(a.x, a.y, a.z, b.x, b.y, b.z, o, inv, tmax);
-      float tr = box_enter(a.w, b.w, c.x, c.y, c.z, c.w, o, inv, tmax);
-      const int cl = lk.x, cr = lk.y;
-      if (tl != F_INF && cl < 0) {
-        pa = ~cl;
-        tl = F_INF;
-      }
-      if (tr != F_INF && cr < 0) {
-        if (pa < 0) pa = ~cr;
-        else pb = ~cr;
-        tr = F_INF;
-      }
-      if (tl != F_INF && tr != F_INF) {
-        const bool lfirst = tl <= tr;
-        stk.put(sp, lfirst ? cr : cl);
-        sp = min(sp + 1, RT0_BVH_STACK - 1);  // the build guarantees depth < RT0_BVH_STACK
-        node = lfirst ? cl : cr;
-      } else if (tl != F_INF) {
-        node = cl;
-      } else if (tr != F_INF) {
-        node = cr;
-      } else if (sp == 0) {
-        node = -1;
-      } else {
-        node = stk.get(--sp);
-      }
-      // a ray visits each node at most once: the cap only guarantees that
-      // every wave drains even on a corrupt tree
-      if (++guard > 2 * P.n_tris + 8) node = -1;
+    if (have && pa < 0 && wk.node >= 0) {
+      const BvhVisit v = wk.visit(P, o, inv, tmax);
+      pa = v.l0;
+      pb = v.l1;
+      wk.next(P, v);
     }
     // leaf phase: once half the busy lanes hold leaves, or no busy lane can
     // visit a node without testing its leaves first
     const uint64_t busy = __ballot(have), lf = __ballot(have && pa >= 0),
-                   stuck = __ballot(have && (pa >= 0 || node < 0));
+                   stuck = __ballot(have && (pa >= 0 || wk.node < 0));
     bool occ = false;
     if ((2 * __popcll(lf) >= __popcll(busy) || stuck == busy) && have && pa >= 0) {
       float t;
       occ = tri_test(tris[pa], o, d, tmax, t) || (pb >= 0 && tri_test(tris[pb], o, d, tmax, t));
       pa = pb = -1;
     }
-    if (have && (occ || (pa < 0 && node < 0))) {
+    if (have && (occ || (pa < 0 && wk.node < 0))) {
       P.walk_res[slot2] = occ ? 1u : 0u;
       j = atomicAdd(ctr, 1u);
       load();
     }
   }
-}
-
-DEV void walk_body(const LaunchParams &P) {
-#if RT0_WALK_SPEC
-  walk_body_spec(P);
-#else
-  treelet_load(P);
-  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
-  if (w >= (uint32_t)P.walk_waves) return;
-  const uint32_t n = P.walk_count[w];
-  const WalkJob *__restrict__ jobs = P.walk_jobs + (size_t)w * (2u * RT0_NEE_REGIONS * (uint32_t)P.nee_cap);
-  uint32_t *ctr = nee_wave_counter();
-  *(volatile uint32_t *)ctr = 64u;  // every lane stores the same value: jobs 0..63 go by lane index
-  const float4 *__restrict__ nodes = reinterpret_cast<const float4 *>(P.bvh);
-  const TriDev *__restrict__ tris = P.tris;
-  BvhStack stk;
-  uint32_t j = threadIdx.x & 63u;
-  bool have = j < n;
-  v3 o = mk(0.f, 0.f, 0.f), d = o, inv = o;
-  float tmax = 0.f;
-  uint32_t slot2 = 0;
-  int node = 0, sp = 0, guard = 0;
-  if (have) {
-    const WalkJob jb = jobs[j];
-    o = mk(jb.ox, jb.oy, jb.oz);
-    d = mk(jb.dx, jb.dy, jb.dz);
-    inv = mk(frcp(d.x), frcp(d.y), frcp(d.z));
-    tmax = jb.tmax;
-    slot2 = jb.slot2;
-  }
-  while (__ballot(have) != 0ull) {
-    if (have) {
-      bool done = false, occ = false;
-      float4 a, b, c;
-      int4 lk;
-      bvh_fetch(P, nodes, node, a, b, c, lk);
-      float tl = box_enter(a.x, a.y, a.z, b.x, b.y, b.z, o, inv, tmax);
-      float tr = box_enter(a.w, b.w, c.x, c.y, c.z, c.w, o, inv, tmax);
-      const int cl = lk.x, cr = lk.y;
-      int l0 = -1, l1 = -1;
-      if (tl != F_INF && cl < 0) {
-        l0 = ~cl;
-        tl = F_INF;
-      }
-      if (tr != F_INF && cr < 0) {
-        if (l0 < 0) l0 = ~cr;
-        else l1 = ~cr;
-        tr = F_INF;
-      }
-      if (l0 >= 0) {
-        float t;
-        occ = tri_test(tris[l0], o, d, tmax, t) || (l1 >= 0 && tri_test(tris[l1], o, d, tmax, t));
-      }
-      if (occ) {
-        done = true;
-      } else if (tl != F_INF && tr != F_INF) {
-        const bool lfirst = tl <= tr;
-        stk.put(sp, lfirst ? cr : cl);
-        sp = min(sp + 1, RT0_BVH_STACK - 1);  // the build guarantees depth < RT0_BVH_STACK
-        node = lfirst ? cl : cr;
-      } else if (tl != F_INF) {
-        node = cl;
-      } else if (tr != F_INF) {
-        node = cr;
-      } else if (sp == 0) {
-        done = true;
-      } else {
-        node = stk.get(--sp);
-      }
-      // a ray visits each node at most once: the cap only guarantees that
-      // every wave drains even on a corrupt tree
-      if (++guard > 2 * P.n_tris + 8) done = true;
-      if (done) {
-        P.walk_res[slot2] = occ ? 1u : 0u;
-        j = atomicAdd(ctr, 1u);
-        have = j < n;
-        if (have) {
-          const WalkJob jb = jobs[j];
-          o = mk(jb.ox, jb.oy, jb.oz);
-          d = mk(jb.dx, jb.dy, jb.dz);
-          inv = mk(frcp(d.x), frcp(d.y), frcp(d.z));
-          tmax = jb.tmax;
-          slot2 = jb.slot2;
-          node = 0;
-          sp = 0;
-          guard = 0;  // (stale stack entries are never read: sp restarts at 0)
-        }
-      }
-    }
-  }
-#endif
 }
 
 #endif
@@ -4175,13 +4084,13 @@ DEV void wf_walk_body(const LaunchParams &P) {
   WfQueue Q(P, pl);
   if (Q.surplus()) return;
   Q.start();
-  const float4 *__restrict__ nodes = reinterpret_cast<const float4 *>(P.bvh);
   const TriDev *__restrict__ tris = P.tris;
-  BvhStack stk;
+  BvhWalk wk;
+  wk.start(P);
   bool busy = false;
   v3 o = mk(0.f, 0.f, 0.f), d = o, inv = o;
   float tmin = 0.f;
-  int node = 0, sp = 0, guard = 0, best = -1;
+  int best = -1;
   uint32_t idx = 0;
   auto take = [&](uint32_t j) {
     const size_t k = (size_t)Q.reg * R + j;
@@ -4192,9 +4101,7 @@ DEV void wf_walk_body(const LaunchParams &P) {
     inv = mk(frcp(d.x), frcp(d.y), frcp(d.z));
     idx = (uint32_t)k;
     busy = tmin >= 0.0f;  // (an entry without a walk: only its light sampling goes on)
-    node = 0;
-    sp = 0;
-    guard = 0;
+    wk.start(P);
     best = -1;
   };
   while (true) {
@@ -4203,52 +4110,19 @@ DEV void wf_walk_body(const LaunchParams &P) {
     if (__popcll(fr) >= RT0_WF_WALK_REFILL || __ballot(busy) == 0ull) Q.refill(fr, [&]() { return busy; }, take);
     if (__ballot(busy) == 0ull) break;  // the queue is dry and every lane answered
     if (busy) {
-      bool done = false;
-      float4 a, b, c;
-      int4 lk;
-      bvh_fetch(P, nodes, node, a, b, c, lk);
-      float tl = box_enter(a.x, a.y, a.z, b.x, b.y, b.z, o, inv, tmin);
-      float tr = box_enter(a.w, b.w, c.x, c.y, c.z, c.w, o, inv, tmin);
-      const int cl = lk.x, cr = lk.y;
-      int l0 = -1, l1 = -1;
-      if (tl != F_INF && cl < 0) {
-        l0 = ~cl;
-        tl = F_INF;
-      }
-      if (tr != F_INF && cr < 0) {
-        if (l0 < 0) l0 = ~cr;
-        else l1 = ~cr;
-        tr = F_INF;
-      }
-      if (l0 >= 0) {
+      const BvhVisit v = wk.visit(P, o, inv, tmin);
+      if (v.l0 >= 0) {
         float t;
-        if (tri_test(tris[l0], o, d, tmin, t)) {
+        if (tri_test(tris[v.l0], o, d, tmin, t)) {
           tmin = t;
-          best = l0;
+          best = v.l0;
         }
-        if (l1 >= 0 && tri_test(tris[l1], o, d, tmin, t)) {
+        if (v.l1 >= 0 && tri_test(tris[v.l1], o, d, tmin, t)) {
           tmin = t;
-          best = l1;
+          best = v.l1;
         }
       }
-      if (tl != F_INF && tr != F_INF) {
-        const bool lfirst = tl <= tr;
-        stk.put(sp, lfirst ? cr : cl);
-        sp = min(sp + 1, RT0_BVH_STACK - 1);  // the build guarantees depth < RT0_BVH_STACK
-        node = lfirst ? cl : cr;
-      } else if (tl != F_INF) {
-        node = cl;
-      } else if (tr != F_INF) {
-        node = cr;
-      } else if (sp == 0) {
-        done = true;
-      } else {
-        node = stk.get(--sp);
-      }
-      // a ray visits each node at most once: the cap only guarantees that
-      // every wave drains even on a corrupt tree
-      if (++guard > 2 * P.n_tris + 8) done = true;
-      if (done) {
+      if (!wk.next(P, v)) {
         P.wf_res[idx] = make_float4(tmin, __int_as_float(best), 0.f, 0.f);
         busy = false;
       }

@@ -1,7 +1,10 @@
 """The walks that only run inside a render -- `walk_body`, `nee_body`'s inline
 occlusion walk, the wavefront walk (rt0_integrator.h) -- on the hard meshes
 of tests/test_trace.py, at image level: they are compiled per scene and
-cannot be called from the ray-query hook.
+cannot be called from the ray-query hook.  Their node visit and choice of the
+next node is the hook's own (`BvhWalk`, shared with `bvh_closest`); what is
+theirs alone -- pending leaves, job and queue refills, the result stores --
+shows only here.
 
 Mask scenes: BASELINE config 5's scene with its model replaced by the cube, a
 flat grid and the stadium, against the oracle's brute-force loop over every
