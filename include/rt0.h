@@ -134,6 +134,46 @@ int rt0_get_scene(const rt0_ctx *ctx, rt0_mesh *meshes, int max_meshes, int *n_m
 int rt0_set_model(rt0_ctx *ctx, int model, const float *positions, int n_vertices, const int32_t *indices,
                   int n_triangles);
 int rt0_model_info(rt0_ctx *ctx, int *n_triangles, int *bvh_depth);
+/* Deforming models: new object-space positions for model k, with the vertex
+ * count and the triangles of the last rt0_set_model(k) (cloth, a morph
+ * target, a skinned mesh).  With a built tree the call enqueues a refit on
+ * the context's stream, ordered before the next render, trace or read-back
+ * (rt0_refit.hip): every triangle record and every box is recomputed on the
+ * device from the new vertices, while the tree's links, leaf order and depth,
+ * the two device arrays and the scene-specialised kernel stay as they are --
+ * no host build, no allocation, no recompilation.  The refitted tree is
+ * exact (each box is the fp32 min/max of what it bounds) but never better
+ * than the build's: after a large deformation rt0_set_model rebuilds.  If the
+ * tree is not built or a model or the scene changed since, or the instance
+ * has joker.x == 0 or no triangles, the positions are only stored and the
+ * next render builds as after rt0_set_model.
+ * rt0_update_model copies from the host and returns when the copy is done.
+ * rt0_update_model_device reads n_vertices x 3 contiguous floats of device
+ * memory on the context's device, on the context's stream (the caller orders
+ * its writes before that stream and keeps the memory until the stream has
+ * passed the call): no host round trip; the host copy a later rebuild needs
+ * is fetched at that rebuild.
+ * The accumulator and the ReSTIR history are the caller's business, as with
+ * a camera move: rt0_clear where no ghosting is wanted.
+ * RT0_E_ARG: model k was never set, or n_vertices differs from its count;
+ * RT0_E_STATE: no scene set. */
+int rt0_update_model(rt0_ctx *ctx, int model, const float *positions, int n_vertices);
+int rt0_update_model_device(rt0_ctx *ctx, int model, const void *d_positions, int n_vertices);
+/* Where every leaf-order triangle (rt0_trace_rays' tri_out, the TriDev order
+ * of rt0_debug_read_bvh) came from: model_out[i] = its model k, tri_out[i] =
+ * its triangle within that model's indices; n_triangles entries each
+ * (rt0_model_info), either may be NULL.  Builds the BVH first if needed. */
+int rt0_model_leaf_source(rt0_ctx *ctx, int32_t *model_out, int32_t *tri_out);
+/* Host-only helper of the refit (no device call): the inner nodes of a node
+ * array as rt0_debug_read_bvh returns it (n_triangles leaves, max(1,
+ * n_triangles - 1) nodes) sorted by height -- 0 for a node whose children
+ * are both leaves, else 1 + its higher inner child -- into order_out, with
+ * group_out[h] = where height h starts (*n_groups + 1 entries, at most nodes
+ * + 1), parent_out / height_out per node (parent -1 for the root); any
+ * output may be NULL.  RT0_E_ARG for an array that is not one tree over its
+ * leaves. */
+int rt0_bvh_height_order(const void *nodes, int n_triangles, int32_t *order_out, int32_t *group_out, int *n_groups,
+                         int32_t *parent_out, int32_t *height_out);
 /* Test hooks of the triangle path (not used by any renderer).
  * Ray queries: n rays (origins / dirs = n x 3 floats, tmax = n bounds or NULL
  * for none) through the device code of the walk, one lane per ray; builds
@@ -380,6 +420,10 @@ int rt0_set_wavefront(rt0_ctx *ctx, int mode);
  * code-object size.  err (may be NULL) receives the compiler log. */
 int rt0_jit_compile(const char *scene_text, const char *const *sdf_meshes, int n_sdf, const rt0_config *cfg,
                     size_t *code_size, char *err, size_t err_len);
+/* hipRTC compilations this process has run so far (every context, and
+ * rt0_jit_compile): a render served by the module cache, or one after a change
+ * that leaves the compiled kernel valid (rt0_update_model), adds none. */
+int rt0_jit_compiles(void);
 
 /* Event counters of the last rt0_render call when enabled: [0] intersection()
  * calls, [1] radiance-loop iterations, [2] light-sampling (NEE) calls,

@@ -193,9 +193,10 @@ __global__ void k_depth(int n, const int *__restrict__ parent, int *__restrict__
 
 // Build the LBVH of n world-space triangles (v: 9 floats each, model: owner
 // index) into caller-allocated nodes[max(1, n-1)] and tris[n].  Returns the
-// tree depth (edges root -> deepest leaf) in *depth_out.
+// tree depth (edges root -> deepest leaf) in *depth_out and, with src_out (n
+// entries, host), the input triangle of every leaf-order triangle.
 extern "C" hipError_t rt0_bvh_build(int n, const float *d_v, const int32_t *d_model, float3 lo, float3 hi,
-                                    BvhNode *d_nodes, TriDev *d_tris, int *depth_out,
+                                    BvhNode *d_nodes, TriDev *d_tris, int *depth_out, uint32_t *src_out,
                                     hipStream_t s) {
   if (n <= 0) return hipErrorInvalidValue;
   const float3 ext = make_float3(hi.x - lo.x, hi.y - lo.y, hi.z - lo.z);
@@ -242,6 +243,7 @@ extern "C" hipError_t rt0_bvh_build(int n, const float *d_v, const int32_t *d_mo
   hipLaunchKernelGGL(k_depth, dim3(G), dim3(B), 0, s, n, parent, depth);
   TRY(hipGetLastError());
   TRY(hipMemcpyAsync(depth_out, depth, 4, hipMemcpyDeviceToHost, s));
+  if (src_out) TRY(hipMemcpyAsync(src_out, idx2, (size_t)n * 4, hipMemcpyDeviceToHost, s));
   TRY(hipStreamSynchronize(s));
 out:
   for (void *p : {(void *)code, (void *)code2, (void *)idx, (void *)idx2, (void *)child, (void *)parent, (void *)flag,

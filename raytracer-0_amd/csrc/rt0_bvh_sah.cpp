@@ -202,7 +202,8 @@ struct Builder {
 
 namespace rt0h {
 
-int bvh_build_sah(int n, const float *v, const int32_t *model, std::vector<BvhNode> &nodes, std::vector<TriDev> &tris) {
+int bvh_build_sah(int n, const float *v, const int32_t *model, std::vector<BvhNode> &nodes, std::vector<TriDev> &tris,
+                  std::vector<uint32_t> *leaf_src) {
   if (n <= 0) return -1;
   std::vector<Aabb> box((size_t)n);
   std::vector<float> cen(3 * (size_t)n);
@@ -243,6 +244,7 @@ int bvh_build_sah(int n, const float *v, const int32_t *model, std::vector<BvhNo
     d.eps = 0.001f * std::sqrt(d.e0x * d.e0x + d.e0y * d.e0y + d.e0z * d.e0z) *
             std::sqrt(d.e1x * d.e1x + d.e1y * d.e1y + d.e1z * d.e1z);
   }
+  if (leaf_src) leaf_src->swap(idx);
   return depth;
 }
 

@@ -23,6 +23,7 @@
 #include "rt0_device.h"
 #include "rt0_internal.h"
 #include "rt0_jit.h"
+#include "rt0_refit.h"
 
 extern "C" hipError_t rt0_launch_pass(int variant, const LaunchParams *p, dim3 grid, hipStream_t stream);
 extern "C" hipError_t rt0_launch_tonemap(const float4 *acc, uchar4 *out, int n, float cont, int mode,
@@ -32,7 +33,7 @@ extern "C" hipError_t rt0_launch_trace(const LaunchParams *p, int n, const float
                                        const float *tmax, int mode, float *t_out, int32_t *tri_out,
                                        hipStream_t stream);
 extern "C" hipError_t rt0_bvh_build(int n, const float *d_v, const int32_t *d_model, float3 lo, float3 hi,
-                                    BvhNode *d_nodes, TriDev *d_tris, int *depth_out,
+                                    BvhNode *d_nodes, TriDev *d_tris, int *depth_out, uint32_t *src_out,
                                     hipStream_t s);
 
 // A pass launch with fewer than kTargetWaves waves (16 per SIMD of the 1024
@@ -80,8 +81,23 @@ struct rt0_ctx {
   struct Model {
     std::vector<float> pos;
     std::vector<int32_t> tri;
+    bool set = false;    // rt0_set_model was called for it
+    bool stale = false;  // rt0_update_model_device: the positions are in refit.d_pos, `pos` is fetched before a rebuild
   };
   std::vector<Model> models;
+  // what a refit (rt0_update_model*, rt0_refit.hip) reads, kept from the last
+  // build_bvh: the instanced models' positions and triangles, the leaf ->
+  // (model, triangle) map, the instances and the inner nodes by height
+  struct Refit {
+    float *d_pos = nullptr;
+    int32_t *d_idx = nullptr;
+    int2 *d_leaf = nullptr;
+    RefitInst *d_inst = nullptr;
+    int32_t *d_order = nullptr;
+    std::vector<int32_t> group_off;              // bvh_height_order
+    std::vector<int32_t> vbase;                  // per model: its first vertex in d_pos, -1 = it has no leaves
+    std::vector<int32_t> leaf_model, leaf_tri;   // rt0_model_leaf_source
+  } refit;
   bool bvh_dirty = false;
   BvhNode *d_bvh = nullptr;
   TriDev *d_tris = nullptr;
@@ -196,6 +212,13 @@ static int alloc_buffers(rt0_ctx *c, int w, int h) {
   c->W = w;
   c->H = h;
   return RT0_OK;
+}
+
+static void free_refit(rt0_ctx *c) {
+  auto &R = c->refit;
+  for (void *q : {(void *)R.d_pos, (void *)R.d_idx, (void *)R.d_leaf, (void *)R.d_inst, (void *)R.d_order})
+    if (q) (void)hipFree(q);
+  R = rt0_ctx::Refit();
 }
 
 static int clear_buffers(rt0_ctx *c) {
@@ -319,6 +342,7 @@ void rt0_destroy(rt0_ctx *c) {
   if (c->d_cube) (void)hipFree(c->d_cube);
   if (c->d_bvh) (void)hipFree(c->d_bvh);
   if (c->d_tris) (void)hipFree(c->d_tris);
+  free_refit(c);
   for (auto &s : c->wf_streams)
     if (s) (void)hipStreamDestroy(s);
   if (c->wf_fork) (void)hipEventDestroy(c->wf_fork);
@@ -500,6 +524,8 @@ int rt0_set_model(rt0_ctx *c, int model, const float *positions, int n_vertices,
   if ((int)c->models.size() <= model) c->models.resize(model + 1);
   c->models[model].pos.assign(positions, positions + 3L * n_vertices);
   c->models[model].tri.assign(indices, indices + 3L * n_triangles);
+  c->models[model].set = true;
+  c->models[model].stale = false;
   c->bvh_dirty = true;
   return RT0_OK;
 }
@@ -516,15 +542,40 @@ static bool bvh_builder_sah() {
 }
 static int build_bvh(rt0_ctx *c) {
   c->bvh_dirty = false;
+  // positions that only the device holds (rt0_update_model_device) come back
+  // now, before the buffer they sit in goes
+  for (size_t k = 0; k < c->models.size(); k++) {
+    auto &M = c->models[k];
+    if (!M.stale) continue;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(M.pos.data(), c->refit.d_pos + 3 * (size_t)c->refit.vbase[k], M.pos.size() * sizeof(float),
+                        hipMemcpyDeviceToHost));
+    M.stale = false;
+  }
+  free_refit(c);
   std::vector<float> v;
   std::vector<int32_t> owner;
+  // the refit's inputs, gathered with the soup: every instanced model's
+  // positions and triangles (vertex indices into the concatenation), and per
+  // soup triangle its model and its index in that model / in the concatenation
+  std::vector<float> r_pos;
+  std::vector<int32_t> r_idx, src_model, src_tri, vbase((size_t)c->n_models, -1);
+  std::vector<RefitInst> inst((size_t)c->n_models, RefitInst{});
   float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   for (int k = 0; k < c->n_models; k++) {
     const rt0_mesh &m = c->meshes[c->n_meshes + c->n_sdfs + k];
     if (m.joker[0] == 0.0f || k >= (int)c->models.size()) continue;  // skipped like intersection()'s joker.x == 0
     const auto &M = c->models[k];
     const int32_t tag = k | ((m.mat_opts & 8u) ? RT0_TRI_CULL_BIT : 0);
+    inst[(size_t)k] = RefitInst{m.pos[0], m.pos[1], m.pos[2], m.joker[0], (m.mat_opts & 8u) ? 1 : 0, 0, 0, 0};
+    if (M.tri.size() >= 3) {
+      vbase[(size_t)k] = (int32_t)(r_pos.size() / 3);
+      r_pos.insert(r_pos.end(), M.pos.begin(), M.pos.end());
+    }
     for (size_t t = 0; t + 2 < M.tri.size(); t += 3) {
+      src_model.push_back(k);
+      src_tri.push_back((int32_t)(t / 3));
+      for (int j = 0; j < 3; j++) r_idx.push_back(vbase[(size_t)k] + M.tri[t + j]);
       for (int j = 0; j < 3; j++) {
         const float *p = &M.pos[3 * (size_t)M.tri[t + j]];
         for (int a = 0; a < 3; a++) {
@@ -549,10 +600,11 @@ static int build_bvh(rt0_ctx *c) {
   HIPCHK(c, hipMalloc(&c->d_bvh, (size_t)std::max(1, n - 1) * sizeof(BvhNode)));
   HIPCHK(c, hipMalloc(&c->d_tris, (size_t)n * sizeof(TriDev)));
   int depth = 0;
+  std::vector<BvhNode> nodes;
+  std::vector<uint32_t> leaf_src;
   if (bvh_builder_sah()) {
-    std::vector<BvhNode> nodes;
     std::vector<TriDev> tris;
-    depth = rt0h::bvh_build_sah(n, v.data(), owner.data(), nodes, tris);
+    depth = rt0h::bvh_build_sah(n, v.data(), owner.data(), nodes, tris, &leaf_src);
     c->treelet = rt0h::bvh_treelet_order(nodes, kTreeletNodes);
     HIPCHK(c, hipMemcpy(c->d_bvh, nodes.data(), nodes.size() * sizeof(BvhNode), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->d_tris, tris.data(), tris.size() * sizeof(TriDev), hipMemcpyHostToDevice));
@@ -563,14 +615,46 @@ static int build_bvh(rt0_ctx *c) {
     HIPCHK(c, hipMalloc(&d_owner, owner.size() * sizeof(int32_t)));
     HIPCHK(c, hipMemcpyAsync(d_v, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_owner, owner.data(), owner.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    leaf_src.resize((size_t)n);
     hipError_t e = rt0_bvh_build(n, d_v, d_owner, make_float3(lo[0], lo[1], lo[2]), make_float3(hi[0], hi[1], hi[2]),
-                                 c->d_bvh, c->d_tris, &depth, c->stream);
+                                 c->d_bvh, c->d_tris, &depth, leaf_src.data(), c->stream);
     (void)hipFree(d_v);
     (void)hipFree(d_owner);
     if (e != hipSuccess) return fail(c, RT0_E_HIP, std::string("BVH build: ") + hipGetErrorString(e));
   }
   if (depth >= RT0_BVH_STACK)
     return fail(c, RT0_E_UNSUPPORTED, "BVH depth " + std::to_string(depth) + " exceeds the traversal stack");
+  {  // the refit's resident state; the heights come from the finished node array, whichever builder wrote it
+    auto &R = c->refit;
+    if (nodes.empty()) {  // the device build: one read-back
+      nodes.resize((size_t)std::max(1, n - 1));
+      HIPCHK(c, hipMemcpy(nodes.data(), c->d_bvh, nodes.size() * sizeof(BvhNode), hipMemcpyDeviceToHost));
+    }
+    std::vector<int32_t> order, parent, height;
+    if (!rt0h::bvh_height_order(nodes.data(), n, order, R.group_off, parent, height))
+      return fail(c, RT0_E_STATE, "the built BVH is not a tree over its leaves");
+    std::vector<int2> leaf((size_t)n);
+    R.leaf_model.resize((size_t)n);
+    R.leaf_tri.resize((size_t)n);
+    for (int i = 0; i < n; i++) {
+      const uint32_t s = leaf_src[(size_t)i];
+      if (s >= (uint32_t)n) return fail(c, RT0_E_STATE, "the BVH build's leaf order names a triangle out of range");
+      R.leaf_model[(size_t)i] = src_model[s];
+      R.leaf_tri[(size_t)i] = src_tri[s];
+      leaf[(size_t)i] = make_int2(src_model[s], (int)s);
+    }
+    R.vbase = vbase;
+    auto upload = [&](auto *&dst, const auto &src) {
+      const size_t bytes = src.size() * sizeof(src[0]);
+      hipError_t e = hipMalloc((void **)&dst, bytes);
+      return e != hipSuccess ? e : hipMemcpy(dst, src.data(), bytes, hipMemcpyHostToDevice);
+    };
+    HIPCHK(c, upload(R.d_pos, r_pos));
+    HIPCHK(c, upload(R.d_idx, r_idx));
+    HIPCHK(c, upload(R.d_leaf, leaf));
+    HIPCHK(c, upload(R.d_inst, inst));
+    HIPCHK(c, upload(R.d_order, order));
+  }
   c->n_tris = n;
   c->bvh_depth = depth;
   c->jit_dirty = true;  // the scene-specialised kernel's traversal stack follows the depth
@@ -587,6 +671,82 @@ int rt0_model_info(rt0_ctx *c, int *n_triangles, int *bvh_depth) {
   if (n_triangles) *n_triangles = c->n_tris;
   if (bvh_depth) *bvh_depth = c->bvh_depth;
   return RT0_OK;
+}
+
+int rt0_model_leaf_source(rt0_ctx *c, int32_t *model_out, int32_t *tri_out) {
+  if (!c) return RT0_E_ARG;
+  if (c->has_scene && c->bvh_dirty) {
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = build_bvh(c);
+    if (rc != RT0_OK) return rc;
+  }
+  const auto &R = c->refit;
+  if (model_out) std::copy(R.leaf_model.begin(), R.leaf_model.end(), model_out);
+  if (tri_out) std::copy(R.leaf_tri.begin(), R.leaf_tri.end(), tri_out);
+  return RT0_OK;
+}
+
+// New positions for model k, from the host (h_pos) or from the context's
+// device (d_pos).  With a built tree that holds the model's triangles the
+// refit is enqueued on the context's stream (rt0_refit.hip): the tree's links,
+// leaf order, depth and both allocations stay, so neither bvh_dirty nor
+// jit_dirty is touched.  Otherwise the positions are only stored.
+static int update_model(rt0_ctx *c, int model, const float *h_pos, const void *d_pos, int n_vertices) {
+  if (!c) return RT0_E_ARG;
+  if (model < 0 || model >= (int)c->models.size() || !c->models[(size_t)model].set)
+    return fail(c, RT0_E_ARG, "rt0_update_model: model " + std::to_string(model) + " was never set (rt0_set_model)");
+  auto &M = c->models[(size_t)model];
+  if (n_vertices < 0 || (size_t)n_vertices * 3 != M.pos.size())
+    return fail(c, RT0_E_ARG, "rt0_update_model: " + std::to_string(n_vertices) + " vertices, the model has " +
+                                  std::to_string(M.pos.size() / 3));
+  if (n_vertices > 0 && !h_pos && !d_pos) return fail(c, RT0_E_ARG, "rt0_update_model: positions is NULL");
+  if (!c->has_scene) return fail(c, RT0_E_STATE, "rt0_update_model before rt0_set_scene*");
+  const size_t bytes = M.pos.size() * sizeof(float);
+  if (bytes == 0) return RT0_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  auto &R = c->refit;
+  const bool live = !c->bvh_dirty && c->n_tris > 0 && (size_t)model < R.vbase.size() && R.vbase[(size_t)model] >= 0;
+  if (h_pos) {
+    M.pos.assign(h_pos, h_pos + M.pos.size());
+    M.stale = false;
+  }
+  if (!live) {  // the next build gathers from the host copy
+    if (!h_pos) {
+      HIPCHK(c, hipMemcpyAsync(M.pos.data(), d_pos, bytes, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      M.stale = false;
+    }
+    return RT0_OK;
+  }
+  float *dst = R.d_pos + 3 * (size_t)R.vbase[(size_t)model];
+  if (h_pos) {
+    // (waits for the copy: M.pos may be assigned again before a pageable copy would have left it)
+    HIPCHK(c, hipMemcpyAsync(dst, M.pos.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  } else {
+    HIPCHK(c, hipMemcpyAsync(dst, d_pos, bytes, hipMemcpyDeviceToDevice, c->stream));
+    M.stale = true;  // fetched before the next build_bvh, not here
+  }
+  RefitDev r;
+  r.pos = R.d_pos;
+  r.idx = R.d_idx;
+  r.leaf = R.d_leaf;
+  r.inst = R.d_inst;
+  r.order = R.d_order;
+  r.nodes = c->d_bvh;
+  r.tris = c->d_tris;
+  r.n_tris = c->n_tris;
+  r.host_eps = bvh_builder_sah() ? 1 : 0;
+  HIPCHK(c, rt0_refit_launch(&r, R.group_off.data(), (int)R.group_off.size() - 1, c->stream));
+  return RT0_OK;
+}
+
+int rt0_update_model(rt0_ctx *c, int model, const float *positions, int n_vertices) {
+  return update_model(c, model, positions, nullptr, n_vertices);
+}
+
+int rt0_update_model_device(rt0_ctx *c, int model, const void *d_positions, int n_vertices) {
+  return update_model(c, model, nullptr, d_positions, n_vertices);
 }
 
 // Test hook: rays through the walk's device code (rt0_kernels.hip

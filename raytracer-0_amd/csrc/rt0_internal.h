@@ -20,8 +20,10 @@ int parse_obj(const char *text, size_t len, std::vector<float> &pos, std::vector
 void default_config(rt0_config &c);
 // binned-SAH BVH (rt0_bvh_sah.cpp) of n triangles (v: 9 floats each, model:
 // owner tags with RT0_TRI_CULL_BIT) -> pre-order inner nodes + leaf-order
-// triangles; returns the depth (edges root -> deepest leaf), -1 for n <= 0
-int bvh_build_sah(int n, const float *v, const int32_t *model, std::vector<BvhNode> &nodes, std::vector<TriDev> &tris);
+// triangles; returns the depth (edges root -> deepest leaf), -1 for n <= 0;
+// leaf_src (optional) = the input triangle of every leaf-order triangle
+int bvh_build_sah(int n, const float *v, const int32_t *model, std::vector<BvhNode> &nodes, std::vector<TriDev> &tris,
+                  std::vector<uint32_t> *leaf_src = nullptr);
 // renumber the tree so that every node of its top levels comes first,
 // breadth-first (at most max_nodes of them, whole levels), the rest after in
 // their pre-order; returns how many lead (the LDS treelet, bvh_fetch)

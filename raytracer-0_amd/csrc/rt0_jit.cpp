@@ -16,6 +16,7 @@
 #include <hip/hiprtc.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -297,7 +298,12 @@ static const Rtc &rtc() {
   return r;
 }
 
+// hipRTC compilations this process has run (rt0_jit_compiles): a cached
+// module, or a change that leaves the kernel valid, does not count
+static std::atomic<int> g_compiles{0};
+
 int jit_compile(const std::string &src, std::vector<char> &code, std::string &err) {
+  g_compiles++;
   const Rtc &R = rtc();
   if (!R.error.empty()) {
     err = R.error;
@@ -539,3 +545,5 @@ extern "C" int rt0_jit_compile(const char *scene_text, const char *const *sdf_me
   }
   return rc;
 }
+
+extern "C" int rt0_jit_compiles(void) { return rt0h::g_compiles.load(); }

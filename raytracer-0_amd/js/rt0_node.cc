@@ -417,6 +417,26 @@ static napi_value SetModel(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
+// updateModel(h, k, positions: Float32Array (3/vertex)): rt0_update_model, the refit of a deforming model
+static napi_value UpdateModel(napi_env env, napi_callback_info info) {
+  napi_value argv[3];
+  if (!get_args(env, info, 3, argv)) return nullptr;
+  CTX_OR_THROW(argv[0]);
+  int32_t k = 0;
+  napi_get_value_int32(env, argv[1], &k);
+  void *pd = nullptr;
+  size_t pl = 0, off = 0;
+  napi_typedarray_type pt;
+  napi_value ab;
+  bool ta = false;
+  napi_is_typedarray(env, argv[2], &ta);
+  if (!ta) return throw_rt0(env, RT0_E_ARG, "positions must be a Float32Array");
+  NAPI_OK(env, napi_get_typedarray_info(env, argv[2], &pt, &pl, &pd, &ab, &off));
+  if (pt != napi_float32_array || pl % 3) return throw_rt0(env, RT0_E_ARG, "positions: Float32Array of xyz");
+  RC_OR_THROW(rt0_update_model(c, k, (const float *)pd, (int)(pl / 3)));
+  return nullptr;
+}
+
 // readObj(path) -> {positions: Float32Array, indices: Int32Array}
 static napi_value ReadObj(napi_env env, napi_callback_info info) {
   napi_value argv[1];
@@ -542,6 +562,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"readImage", nullptr, ReadPng, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"setCubemap", nullptr, SetCubemap, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"setModel", nullptr, SetModel, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"updateModel", nullptr, UpdateModel, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"readObj", nullptr, ReadObj, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);

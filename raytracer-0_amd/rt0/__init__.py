@@ -32,7 +32,9 @@ EXPORTS = ["rt0_create", "rt0_destroy", "rt0_last_error", "rt0_parse_config", "r
            "rt0_set_halo", "rt0_read_halo_misses", "rt0_set_jit", "rt0_set_executor_compat", "rt0_set_texture_filter", "rt0_set_defer_light_sampling", "rt0_set_wavefront", "rt0_jit_compile", "rt0_set_counting",
            "rt0_read_counters", "rt0_read_counters_n", "rt0_last_kernel_ms", "rt0_last_render_path", "rt0_version", "rt0_tonemap_ex", "rt0_png_decode", "rt0_png_read",
            "rt0_png_write", "rt0_pfm_write", "rt0_free", "rt0_set_texture", "rt0_set_cubemap", "rt0_jpeg_decode", "rt0_jpeg_read", "rt0_set_model", "rt0_model_info", "rt0_obj_read",
-           "rt0_set_temporal_frames", "rt0_set_viewport", "rt0_scratch_bytes", "rt0_trace_rays", "rt0_debug_read_bvh"]
+           "rt0_set_temporal_frames", "rt0_set_viewport", "rt0_scratch_bytes", "rt0_trace_rays", "rt0_debug_read_bvh",
+           "rt0_update_model", "rt0_update_model_device", "rt0_model_leaf_source", "rt0_bvh_height_order",
+           "rt0_jit_compiles"]
 
 TEX_NOISE = 4  # RT0_TEX_NOISE: the u_rnd_tex unit of rt0_set_texture
 TONEMAP_GAMMA, TONEMAP_ACES, TONEMAP_REINHARD = 0, 1, 2
@@ -101,6 +103,12 @@ def lib():
                                   P(c_int)]),
         "rt0_set_model": (c_int, [c_void_p, c_int, fp, c_int, P(ctypes.c_int32), c_int]),
         "rt0_model_info": (c_int, [c_void_p, P(c_int), P(c_int)]),
+        "rt0_update_model": (c_int, [c_void_p, c_int, fp, c_int]),
+        "rt0_update_model_device": (c_int, [c_void_p, c_int, c_void_p, c_int]),
+        "rt0_model_leaf_source": (c_int, [c_void_p, P(ctypes.c_int32), P(ctypes.c_int32)]),
+        "rt0_bvh_height_order": (c_int, [c_void_p, c_int, P(ctypes.c_int32), P(ctypes.c_int32), P(c_int),
+                                         P(ctypes.c_int32), P(ctypes.c_int32)]),
+        "rt0_jit_compiles": (c_int, []),
         "rt0_trace_rays": (c_int, [c_void_p, c_int, fp, fp, fp, c_int, fp, P(ctypes.c_int32)]),
         "rt0_debug_read_bvh": (c_int, [c_void_p, c_void_p, c_void_p, P(c_int)]),
         "rt0_obj_read": (c_int, [ctypes.c_char_p, P(fp), P(c_int), P(P(ctypes.c_int32)), P(c_int)]),
@@ -271,6 +279,32 @@ def pfm_write(path, rgba, scale=1.0):
     _check_io(lib().rt0_pfm_write(str(path).encode(), a.shape[1], a.shape[0], _fp(a), scale), "pfm_write")
 
 
+def jit_compiles():
+    """hipRTC compilations of this process so far (rt0_jit_compiles)."""
+    return lib().rt0_jit_compiles()
+
+
+def bvh_height_order(nodes, n_triangles):
+    """The refit's order of a node array (Renderer.BVH_NODE records, as
+    read_bvh returns them): (order, group offsets, parent, height) int32
+    arrays (rt0_bvh_height_order; host only).  Raises Rt0Error(RT0_E_ARG) for
+    an array that is not one tree over its leaves."""
+    nodes = np.ascontiguousarray(nodes)
+    n = max(1, n_triangles - 1)
+    if nodes.nbytes != 64 * n:
+        raise ValueError("%d nodes of 64 B expected" % n)
+    order, parent, height = (np.empty(n, np.int32) for _ in range(3))
+    group = np.empty(n + 1, np.int32)
+    ng = ctypes.c_int()
+    i32 = ctypes.POINTER(ctypes.c_int32)
+    rc = lib().rt0_bvh_height_order(nodes.ctypes.data_as(ctypes.c_void_p), n_triangles, order.ctypes.data_as(i32),
+                                    group.ctypes.data_as(i32), ctypes.byref(ng), parent.ctypes.data_as(i32),
+                                    height.ctypes.data_as(i32))
+    if rc != RT0_OK:
+        raise Rt0Error(rc, "not a tree over %d leaves" % n_triangles)
+    return order, group[:ng.value + 1].copy(), parent, height
+
+
 def jit_compile(scene_text, sdf_meshes, cfg):
     """Build the scene-specialised kernel offline (hipRTC, no device); returns the code-object size."""
     sdf = list(sdf_meshes)
@@ -343,6 +377,8 @@ class Renderer:
             raise Rt0Error(rc, "rt0_create(%d, %d, device=%d) failed (no HIP device?)" % (width, height, device))
         self.h = h
         self.width, self.height = width, height
+        self.device = device
+        self._ext_stream = None  # the context's stream as a torch stream (update_model)
 
     def _chk(self, rc):
         if rc != RT0_OK:
@@ -392,6 +428,52 @@ class Renderer:
         n, d = ctypes.c_int(), ctypes.c_int()
         self._chk(lib().rt0_model_info(self.h, ctypes.byref(n), ctypes.byref(d)))
         return n.value, d.value
+
+    def update_model(self, k, positions):
+        """New object-space positions [nv, 3] for model k, the vertex count and
+        triangles of set_model(k) (rt0_update_model*): with a built tree a
+        device-side refit, no rebuild and no recompilation.  A numpy array or
+        a CPU tensor is copied from the host; a float32 contiguous torch tensor
+        on the context's GPU is read in place on the context's stream, ordered
+        after torch's current stream, which in turn waits for that read (so the
+        tensor needs no keeping).  clear() where no ghosting is wanted."""
+        if type(positions).__module__.split(".")[0] == "torch":
+            import torch
+            t = positions
+            if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous():
+                raise ValueError("positions: a contiguous float32 [nv, 3] tensor expected")
+            if t.is_cuda:
+                if t.device.index != self.device:
+                    raise ValueError("positions are on %s, the context on GPU %d" % (t.device, self.device))
+                if self._ext_stream is None:
+                    self._ext_stream = torch.cuda.ExternalStream(self.device_accum()[1], device=t.device)
+                cur = torch.cuda.current_stream(t.device)
+                ev = torch.cuda.Event()
+                ev.record(cur)
+                self._ext_stream.wait_event(ev)
+                self._chk(lib().rt0_update_model_device(self.h, k, ctypes.c_void_p(t.data_ptr()), t.shape[0]))
+                # torch's stream goes on after the copy: the tensor may be freed or overwritten
+                # there at once.  (Not record_stream: the allocator would then touch the context's
+                # stream when the tensor is freed, which may be after close().)
+                ev = torch.cuda.Event()
+                ev.record(self._ext_stream)
+                cur.wait_event(ev)
+                return
+            positions = t.numpy()
+        v = np.ascontiguousarray(positions, np.float32)
+        if v.ndim != 2 or v.shape[1] != 3:
+            raise ValueError("positions: [nv, 3] expected")
+        self._chk(lib().rt0_update_model(self.h, k, _fp(v), v.shape[0]))
+
+    def leaf_source(self):
+        """(model k, triangle within that model) int32 [n] of every leaf-order
+        triangle (rt0_model_leaf_source): what trace_rays' triangle indices and
+        read_bvh's triangle records refer to."""
+        n, _ = self.model_info()
+        model, tri = np.empty(n, np.int32), np.empty(n, np.int32)
+        i32 = ctypes.POINTER(ctypes.c_int32)
+        self._chk(lib().rt0_model_leaf_source(self.h, model.ctypes.data_as(i32), tri.ctypes.data_as(i32)))
+        return model, tri
 
     def set_scene(self, meshes, n_meshes, n_sdfs, n_models, lights):
         """Test hook: rt0_set_scene from flattened records, e.g. get_scene()'s
