@@ -142,6 +142,15 @@ DEV float flog(float x) { return __logf(x); }
 #ifndef RT0_WF_UNIT  // entries a march wave takes per device-counter grab, about (wf_march_body)
 #define RT0_WF_UNIT 256
 #endif
+// A path that hits a light ends there: the plain pass kernel notes the hit in
+// step() and evaluates its contribution once per sample at the wave's
+// convergent point before accumulate (Integrator::path_end) instead of inside
+// the bounce loop, where the block ran about four times per wave and sample
+// for about one lane each.  0 = the inline form (the A/B handle and the
+// bit-identity reference, tests/test_gpu_path_end.py)
+#ifndef RT0_PATH_END_DEFER
+#define RT0_PATH_END_DEFER 1
+#endif
 DEV float nc_fract(float x) {
 #pragma clang fp contract(off)
   return x - floorf(x);
@@ -2455,15 +2464,15 @@ struct Integrator {
   }
 
   // radiance() + brdf(), raytracer.glsl:1986-2105 and 1804-1980, as a step
-  // function: one iteration of the bounce loop per call, so that a lane whose
-  // path ended can start its next sample while the rest of its wave is still
-  // bouncing (path regeneration in pass_body).  The path state is what the
-  // shader keeps across iterations.
+  // function: one iteration of the bounce loop per call, for the callers that
+  // interleave bounces with other work (the march loop below, the wavefront
+  // kernels' rounds).  The path state is what the shader keeps across
+  // iterations.
   //
-  // SUSP kernels (SDF scenes, path regeneration, no ReSTIR): a sphere-tracing
+  // SUSP kernels (SDF scenes in the pass kernel, no ReSTIR): a sphere-tracing
   // march runs at most RT0_MARCH_BUDGET steps per call.  A lane whose march is
   // unfinished returns from step() and resumes it at its next call, while the
-  // other lanes of its wave go on with their own bounces and samples -- so one
+  // other lanes of its wave go on with their own bounces -- so one
   // long march no longer holds 63 finished lanes idle.  A bounce is two
   // phases: 0 = its ray (and the shading that follows), 1 = its light
   // sampling (one shadow ray per light), each resumable; every lane still
@@ -2492,7 +2501,80 @@ struct Integrator {
     int phase;  // SUSP only
     March ms;
     NeeCtx nc;
+    // defer_end(): the light the path ended on (mesh index + 1; 0 = it ended
+    // otherwise) and the hit's t -- all path_end() needs beside the registers
+    // above, which stand as the last bounce left them once step() returns false
+    int end_mesh;
+    float end_t;
   };
+  // The plain pass instance evaluates a light hit in path_end() instead of
+  // step() (RT0_PATH_END_DEFER).  Every term is compile-time or wave-uniform.
+  // Textured scenes keep the inline form: the light's colour there is a texel
+  // at the hit, which path_end() does not have.
+  DEV bool defer_end() const {
+    if constexpr (!RT0_PATH_END_DEFER || RESTIR || COUNT || SUSP || WF || WFB) return false;
+    else return !ghost_on() && !quad_rec() && !sc.any_tex();
+  }
+  // The end of a path that hit a light, for the lanes step() flagged: the
+  // inline block's expressions in its order, once per sample where the wave
+  // has reconverged.  ro, rd, mask, prev_nl, depth and spec are the hit
+  // bounce's (a dead lane's registers do not move); the material comes from
+  // the tables step() read, and hit.pos is rebuilt as intersect() formed it.
+  DEV void path_end(Path &ps) {
+    if (!defer_end() || ps.end_mesh == 0) return;
+    const int idx = ps.end_mesh - 1;
+    const GeomRec g = geom_at(idx);
+    const MatRec mt = mat_at(idx);
+    v3 c, e;
+    if constexpr (Scene::kStatic) {  // (defer_end(): no textures, so step() read the clamped records)
+      const MatRec ms = mat_shade_at(idx);
+      c = mk(ms.cr, ms.cg, ms.cb);
+      e = mk(ms.er, ms.eg, ms.eb);
+    } else {
+      c = vmaxs(mk(mt.cr, mt.cg, mt.cb), 0.001f);
+      e = vmaxs(mk(mt.er, mt.eg, mt.eb), 0.001f);
+    }
+    const v3 me = (ps.mask * c) * e;
+    float w = 1.0f;
+    if (flag(F_MIS) && !ps.spec && flag(F_SAMPLE_LIGHTS) && ps.depth > 0) w = light_hit_weight(ps, g, mt);
+    ps.acc = mk(__builtin_fmaf(me.x, w, ps.acc.x), __builtin_fmaf(me.y, w, ps.acc.y), __builtin_fmaf(me.z, w, ps.acc.z));
+  }
+  // step()'s power_heuristic(cos_pdf(normalize(hit.pos - ro), prev_nl),
+  // light_pdf(g, mt, ro)) with every fused multiply-add written out.  Which
+  // product of a sum the compiler contracts depends on the code around it (at
+  // this program point it picked another one for normalize()'s dot than inside
+  // the bounce loop, one ulp apart), so the forms it picks there -- a dot is
+  // fma(z, z', fma(x, x', y * y')), 1 - r2/d2 and g*g + f*f one fma each --
+  // are fixed here: the deferred end gives the inline form's bits.
+  DEV float dot_yxz(v3 a, v3 b) const {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(a.z, b.z, __builtin_fmaf(a.x, b.x, a.y * b.y));
+  }
+  DEV float light_hit_weight(const Path &ps, const GeomRec &g, const MatRec &mt) const {
+#pragma clang fp contract(off)
+    const v3 ro = ps.ro;
+    const v3 pos = mk(__builtin_fmaf(ps.rd.x, ps.end_t, ro.x), __builtin_fmaf(ps.rd.y, ps.end_t, ro.y),
+                      __builtin_fmaf(ps.rd.z, ps.end_t, ro.z));  // intersect()'s hit.pos
+    const v3 d = mk(pos.x - ro.x, pos.y - ro.y, pos.z - ro.z);
+    const float r = frsq(dot_yxz(d, d));
+    const v3 ld = mk(d.x * r, d.y * r, d.z * r);
+    const float f = fmaxf(0.0f, dot_yxz(ld, ps.prev_nl)) * ONE_OVER_PI;  // cos_pdf
+    float lp = 0.0f;                                                      // light_pdf
+    if (mt.type == M_LIGHT) {
+      if (g.type == T_SPHERE) {
+        const v3 dc = mk(g.px - ro.x, g.py - ro.y, g.pz - ro.z);
+        const float d2 = dot_yxz(dc, dc), r2 = g.d0;
+        if (!(d2 <= r2)) {
+          const float den = 1.0f - fsqrt(fmaxf(0.0f, __builtin_fmaf(-r2, frcp(d2), 1.0f)));
+          if (!(den < 1e-6f)) lp = frcp(TWO_PI * den);
+        }
+      } else {
+        lp = 1.0f / FOUR_PI;
+      }
+    }
+    const float ff = f * f;  // power_heuristic
+    return fmaxf(0.0f, ff * frcp(__builtin_fmaf(lp, lp, ff)));
+  }
   DEV March *march_slot(Path &ps) {
     if constexpr (WFB) return (sc.n_models() > 0 && P.n_tris > 0) ? &ps.ms : nullptr;
     if constexpr (!SUSP && !WF) return nullptr;
@@ -2750,6 +2832,11 @@ struct Integrator {
     float inside = -sgn(dot(rd, hit.n));
     if (!pre) e = vmaxs(e, 0.001f);
     if (mt.type == M_LIGHT) {
+      if (defer_end()) {  // path_end() adds this hit's light once the wave's paths have all ended
+        ps.end_mesh = hit.index + 1;
+        ps.end_t = t;
+        return false;
+      }
       mask = mask * c;
       float w = 1.0f;
       if (flag(F_MIS) && !spec && flag(F_SAMPLE_LIGHTS) && depth > 0) {
@@ -2893,6 +2980,7 @@ struct Integrator {
       while (step(ps)) {
         if constexpr (SUSP) march_pending(ps);
       }
+    path_end(ps);
     return ps.acc;
   }
 
@@ -2911,7 +2999,7 @@ struct Integrator {
     sy = nc_seed3(seed, 1234.567f, fr, b, 9876.54f);
   }
   // the pixel's gl_FragCoord and the camera offset that depends on it alone
-  // (once per pixel: path regeneration starts its samples with begin_sample)
+  // (once per pixel: pixel_passes starts its samples with begin_sample)
   DEV void set_pixel(int px, int py) {
     q_px = px;
     q_py = py;
@@ -2977,6 +3065,7 @@ struct Integrator {
       while (step(ps)) {
         if constexpr (SUSP) march_pending(ps);
       }
+    path_end(ps);
     return finish(ps);
   }
 };
@@ -3017,33 +3106,35 @@ DEV size_t sample_index(const LaunchParams &P, int px, int r) {
 // -- were measured and lost or tied, DESIGN 4.7: blockIdx maps straight to
 // the tile.)
 
-// Path regeneration: the lane runs its pixel's passes back to back as ONE
-// loop of bounce steps; when its path ends it accumulates the sample and
-// starts the next pass at once instead of idling until the longest path of
-// its wave has finished.  Each pixel's samples are still produced and summed
-// in pass order, so the result is bit-identical to the plain loop.
+// The lane runs its pixel's passes back to back, the accumulator in
+// registers.  Per pass: the camera ray, bounce steps until the path ends, the
+// deferred light hit (path_end), the sum.  The frame counter is wave-uniform,
+// so the wave reconverges after every pass's bounce loop: a lane whose path
+// ends early idles until its wave's longest path has ended.  (Until round 7
+// this was written as one loop of bounce steps in which a lane started its
+// next pass as soon as its path ended, "path regeneration"; the compiler
+// turned that loop back into this one -- scalar frame counter, exec restored
+// before begin_sample -- which the per-lane semantics allow.  DESIGN 5.000000.)
 template <class It, class Cfg>
-DEV void regen_pixel(const LaunchParams &P, It &it, const Cfg &cfg, int px, int py, size_t apix) {
+DEV void pixel_passes(const LaunchParams &P, It &it, const Cfg &cfg, int px, int py, size_t apix) {
   float4 a = P.accum[apix];
-  if (P.nframes > 0) {
-    typename It::Path ps;
-    int f = 0;
-    it.frame = P.frame0;
-    it.begin(ps, px, py);
-    bool alive = cfg.max_bounces() > 0;
-    while (true) {
-      // a lane whose march is still pending skips step() (its bounce resumes once it is done)
-      if (alive && !(It::SUSP && ps.ms.active)) alive = it.step(ps);
-      if (!alive) {
-        accumulate(it, P, a, it.finish(ps));
-        it.quad_store();  // (rule 11's recording launch: one frame)
-        if (++f >= P.nframes) break;
-        it.frame = P.frame0 + (uint32_t)f;
-        it.begin_sample(ps);  // same pixel: set_pixel's values stand
-        alive = cfg.max_bounces() > 0;
+  typename It::Path ps;
+  it.set_pixel(px, py);
+  for (int f = 0; f < P.nframes; ++f) {
+    it.frame = P.frame0 + (uint32_t)f;
+    it.begin_sample(ps);  // same pixel: set_pixel's values stand
+    if (cfg.max_bounces() > 0) {
+      if constexpr (It::SUSP) {
+        // a lane whose march is still pending skips step() (its bounce resumes once it is done)
+        while (ps.ms.active || it.step(ps)) it.march_pending(ps);
+      } else {
+        while (it.step(ps)) {
+        }
       }
-      if constexpr (It::SUSP) it.march_pending(ps);
     }
+    it.path_end(ps);
+    accumulate(it, P, a, it.finish(ps));
+    it.quad_store();  // (rule 11's recording launch: one frame)
   }
   P.accum[apix] = a;
 }
@@ -3079,7 +3170,7 @@ DEV void pass_body(const LaunchParams &P, Scene sc, Cfg cfg) {
       P.samples[(size_t)f * plane + lp] = make_float4(s.x, s.y, s.z, 0.f);
     }
   } else if constexpr (!RESTIR && !COUNT) {
-    regen_pixel(P, it, cfg, px, py, apix);
+    pixel_passes(P, it, cfg, px, py, apix);
   } else if constexpr (RT0_DEFER_NEE && RESTIR && !COUNT) {
     // the path without its deferred sampleLightsReSTIR calls; rt0_jit_resolve
     // completes the sample and accumulates it

@@ -7,7 +7,9 @@
 # Choose the probe with RT0_JIT_EXTRA, e.g.
 #   scripts/probes.sh env RT0_JIT_EXTRA=-DRT0_EXP_NO_NEE python scripts/exp_c4.py 1024 8 causes
 # Probes: RT0_EXP_NO_BVH_OCC, RT0_EXP_NO_SHADOW, RT0_EXP_SPATIAL_SELF,
-# RT0_EXP_NO_NEE, RT0_EXP_NO_VOL_NEE, RT0_NO_MIS_REUSE, RT0_FAST_SHADOW=0.
+# RT0_EXP_NO_NEE, RT0_EXP_NO_VOL_NEE, RT0_NO_MIS_REUSE, RT0_FAST_SHADOW=0,
+# RT0_EXP_NO_LIGHT_W (a light hit's MIS weight is 1: the ceiling of moving that
+# block, profiles/r07/c2_path_end).
 # Output written under the copy's gpurun_out/ is copied back to this tree's.
 set -e
 ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
